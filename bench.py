@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — train-step images/sec of the ReID-GAN training steps on MI355X (BASELINE.json).
 
-    python bench.py [--config 2|3|4a|4b|5] [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--config 2|3|4a|4b|5] [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 Default (`--config 2`, BASELINE.json configs[1], the configuration the metric is quoted on): one "step" =
 FDGANModel.set_input + optimize_parameters (FD/fdgan/model.py:127-147,216-229) on one batch of synthetic, HBM-resident
@@ -13,33 +13,44 @@ input: batch_size 16 pairs = 32 crops of 256x128 + 18-channel pose maps per GPU,
     4b  joint step with FDGANModel in the GAN role (north-star wording), 32 crops = 16 pairs          (fdgan/adaptor.py)
     5   dual_gan DPTNModel step (two generator branches), fp8 MFMA convolutions, 64 crops at 128x64    (DPTN_model.py:216-225)
 
-and, unless --no-others is given, the default single-GPU run also measures each of them briefly and reports them under
-`other_configs` of the same JSON line, so one driver-run line covers every configuration (multi-GPU runs: the headline
-only, unless --others asks for the DDP configurations 4a / 4b / 5 behind it).
+A plain run sets up, warms up, times the K steps and prints the line: `metric`, `value` (images/s), `unit`,
+`higher_is_better`, `dtype` and `ms_per_step` (one timed step).  `--dump-outputs DIR` then also writes what the last timed
+step computed as DIR/<name>.npy (losses float64; generated images and a fixed, seeded sample of every trained network's
+state float32), so two builds can be compared output for output on identical seeded inputs.  With the same arguments the
+outputs are the same bit for bit from run to run: the convolutions run the kernels recorded in CONV_CHOICES (pin_conv_choices).
+
+`--full` adds everything beyond the headline figure: the roofline object, the CPU baseline, and (unless --no-others) each
+of the other configurations measured briefly under `other_configs` of the same JSON line, so one driver-run line covers
+every configuration (multi-GPU runs: the headline only, unless --others asks for the DDP configurations 4a / 4b / 5
+behind it).
 
 Multi-GPU: weak scaling, one rank per GPU, gradients all-reduced over RCCL.  `--gpus N` without a torch.distributed
 environment starts the N ranks itself (a `python -m torch.distributed.run` child process, created before this process
 makes any GPU call) and relays rank 0's line; under `torch.distributed.run` it reads RANK / LOCAL_RANK / WORLD_SIZE.
 
-Rank 0 prints ONE JSON line.  `roofline` is measured live with HIP events recorded by the library around every conv
+Rank 0 prints ONE JSON line.  With --full, `roofline` is measured live with HIP events recorded by the library around every conv
 implicit-GEMM launch (on the launch stream) during `--profile-steps` extra steps that follow the timed region, run by
 EVERY rank (their collectives must match) with the kernels launched back to back on one stream; `cpu_baseline` times the
-CPU oracle restatement of the same step on the GPU box's host cores (rank 0, N=1 only).
+CPU oracle restatement of the same step on the host cores (rank 0, N=1 only).  Without --full both are null.
 """
 from __future__ import absolute_import, print_function
 
 import argparse
+import atexit
 import json
 import os
+import shutil
 import socket
 import subprocess
 import sys
+import tempfile
 import time
 
 REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(REPO, "reid-gan_amd"))
 sys.path.insert(0, REPO)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
@@ -54,6 +65,7 @@ SPLIT_BF16_PEAK_TFLOPS = round(BF16_MFMA_PEAK_TFLOPS / 6.0, 1)
 F8_MFMA_PEAK_TFLOPS = 5000.0      # dense fp8: v_mfma_scale_f32_32x32x64_f8f6f4 with e4m3 / e5m2 operands runs at twice the
                                   # bf16 rate (same guide, "Matrix cores"); the non-scaled 32x32x16 fp8 forms only reach 2.5 PF
 METRIC = "train-step images/sec, 256×128 ReID batch, 1/2/4/8 MI355X"
+CONV_CHOICES = os.path.join(REPO, "profiles", "conv_choices_mi355x.txt")
 
 
 def log(*a):
@@ -71,6 +83,23 @@ def host_cores():
     except Exception:
         pass
     return max(1, min(n, int(os.environ.get("RG_CPU_THREADS", "16"))))
+
+
+def pin_conv_choices():
+    """The first call of a convolution geometry times its kernel / tile / split-K candidates and keeps the fastest
+    (csrc/conv_igemm.hip, choose_impl).  The candidates sum in different orders, so two processes that choose differently
+    compute outputs that differ in the last bits, and the training steps amplify that.  The benchmark therefore runs the
+    choices recorded in CONV_CHOICES (the same measurement on an MI355X, majority of three runs over every configuration),
+    handed to the library as its RG_CONV_TUNE_CACHE: same arguments, same kernels, same outputs.  A geometry the file lacks is
+    still measured and appended to this process's private copy, never to the committed file.  An RG_CONV_TUNE_CACHE set by the
+    caller wins."""
+    if "RG_CONV_TUNE_CACHE" in os.environ:
+        return
+    fd, path = tempfile.mkstemp(prefix="rg_conv_choices_", suffix=".txt")
+    os.close(fd)
+    shutil.copyfile(CONV_CHOICES, path)
+    atexit.register(os.unlink, path)
+    os.environ["RG_CONV_TUNE_CACHE"] = path
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -175,6 +204,14 @@ class Workload(object):
     def losses(self):
         return {}
 
+    def networks(self):
+        """{name: module} of the networks step() trains (their state after the step is part of its result)"""
+        return {}
+
+    def images(self):
+        """{name: tensor} of the images the step generates"""
+        return {}
+
     def serial(self, on):
         """launch order for the profiled steps: every kernel back to back on one stream"""
         from rg_hip import ops
@@ -220,6 +257,13 @@ class FDGANStep(Workload):
 
     def losses(self):
         return self.model.get_current_errors()
+
+    def networks(self):
+        m = self.model
+        return {"E": m.net_E, "G": m.net_G, "Di": m.net_Di, "Dp": m.net_Dp}
+
+    def images(self):
+        return {"fake": self.model.fake}
 
     def cpu_baseline(self, pairs=16, warm=2, timed=5):
         from oracle import ref_torch as O
@@ -284,6 +328,9 @@ class CCStep(Workload):
     def losses(self):
         return {"loss": float(self.loss)}
 
+    def networks(self):
+        return {"encoder": self.enc, "memory": self.mem}
+
     def cpu_baseline(self, warm=2, timed=5):
         from oracle import ref_torch as O
         cores = host_cores()
@@ -330,6 +377,14 @@ class Joint4a(Workload):
     def losses(self):
         return {"loss": float(self.loss)}
 
+    def networks(self):
+        d = {"encoder": self.enc, "memory": self.mem}
+        d.update(("gan_" + n, getattr(self.gan, "net_" + n)) for n in self.gan.model_names)
+        return d
+
+    def images(self):
+        return {"fake_image": self.gan.fake_image}
+
 
 class Joint4b(Workload):
     key = "4b"
@@ -361,6 +416,13 @@ class Joint4b(Workload):
         d = {"loss": float(self.loss)}
         d.update(self.model.get_current_errors())
         return d
+
+    def networks(self):
+        m = self.model
+        return {"encoder": self.enc, "memory": self.mem, "E": m.net_E, "G": m.net_G, "Di": m.net_Di, "Dp": m.net_Dp}
+
+    def images(self):
+        return {"fake": self.model.fake}
 
 
 class DPTNStep(Workload):
@@ -394,6 +456,12 @@ class DPTNStep(Workload):
     def losses(self):
         return {k: float(v) for k, v in self.gan.get_current_errors().items()}
 
+    def networks(self):
+        return {n: getattr(self.gan, "net_" + n) for n in self.gan.model_names}
+
+    def images(self):
+        return {"fake_image_t": self.gan.fake_image_t, "fake_image_s": self.gan.fake_image_s}
+
     def cpu_baseline(self, warm=1, timed=3):
         from oracle import ref_dualgan as OD
         cores = host_cores()
@@ -412,6 +480,34 @@ WORKLOADS = {w.key: w for w in (FDGANStep, CCStep, Joint4a, Joint4b, DPTNStep)}
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+DUMP_STATE_SAMPLE = 1 << 18       # elements of each network's state written by --dump-outputs (seeded positions)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def collect_outputs(w):
+    """What a caller of w.step() holds after its last call, on the host: the losses (float64), the generated images and a
+    fixed, seeded sample of every trained network's floating-point state after the update (float32)."""
+    out = {"loss_" + k: np.float64(v) for k, v in w.losses().items()}
+    for k, t in w.images().items():
+        out[k] = t.detach().float().cpu().numpy()
+    for k, net in w.networks().items():
+        flat = torch.cat([v.detach().reshape(-1).float() for v in net.state_dict().values() if v.is_floating_point()])
+        if flat.numel() > DUMP_STATE_SAMPLE:
+            idx = torch.randint(0, flat.numel(), (DUMP_STATE_SAMPLE,), generator=torch.Generator().manual_seed(0))
+            flat = flat[idx.sort().values.to(flat.device)]
+        out["state_" + k] = flat.cpu().numpy()
+    nbytes = sum(a.nbytes for a in out.values())
+    assert nbytes <= DUMP_MAX_BYTES, "outputs of config %s: %d bytes" % (w.key, nbytes)
+    return out
+
+
+def dump_outputs(out, path):
+    os.makedirs(path, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    log("wrote %d outputs (%.1f MB) to %s" % (len(out), sum(a.nbytes for a in out.values()) / 1e6, path))
+
+
 def pmc_traffic(key, launches_per_step):
     """HBM bytes per conv launch from the committed PMC passes (profiles/r04_pmc_traffic.json, else an earlier round's; produced on the GPU box by
     tools/prof_summary.py + tools/pmc_traffic.py from separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE runs of this
@@ -436,7 +532,8 @@ def pmc_traffic(key, launches_per_step):
 
 
 def measure(w, args, dev, rank, world, use_dist, headline):
-    """warm-up, timed region (barrier + synchronize on both sides, MAX over ranks), then the profiled steps on every rank"""
+    """warm-up, timed region (barrier + synchronize on both sides, MAX over ranks), the outputs of its last step if asked
+    for, then (--full) the profiled steps on every rank"""
     from rg_hip import ops
     steps, warmup = (args.steps, args.warmup) if headline else (args.other_steps, 3)
 
@@ -470,6 +567,8 @@ def measure(w, args, dev, rank, world, use_dist, headline):
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+    if headline and rank == 0 and args.dump_outputs:
+        dump_outputs(collect_outputs(w), args.dump_outputs)
     losses = w.losses()
     if rank == 0:
         log("config %s: timed %d steps: %.2f ms/step (host enqueue %.2f)" % (w.key, steps, 1e3 * elapsed / steps,
@@ -484,7 +583,7 @@ def measure(w, args, dev, rank, world, use_dist, headline):
 
     # ---- roofline: per-launch HIP events on the conv implicit-GEMM kernels; EVERY rank runs these steps (collectives) ----
     roof = None
-    psteps = args.profile_steps if headline else min(args.profile_steps, 2)
+    psteps = (args.profile_steps if headline else min(args.profile_steps, 2)) if args.full else 0
     if psteps > 0:
         # per-launch durations are taken with the kernels launched back to back on ONE stream: in the timed region the
         # weight-gradient kernels and independent network passes run concurrently on side streams, which lengthens each
@@ -562,8 +661,8 @@ def self_launch(args):
     if args.dry_run:
         print(json.dumps({"dry_run": True, "ranks": args.gpus, "cmd": cmd,
                           "env": {k: env[k] for k in ("HSA_ENABLE_IPC_MODE_LEGACY", "OMP_NUM_THREADS")},
-                          "configs_measured": [args.config] + (OTHERS_DIST if args.others and not args.no_others and args.config == "2"
-                                                                 else [])}),
+                          "configs_measured": [args.config] + (OTHERS_DIST if args.full and args.others and not args.no_others
+                                                                 and args.config == "2" else [])}),
               file=_real_stdout)
         _real_stdout.flush()
         return 0
@@ -582,21 +681,31 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="2", choices=sorted(WORKLOADS))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32 / float64, <= 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the roofline profile steps, the CPU baseline and the "
+                         "other configurations (the options below apply to such a run only)")
     ap.add_argument("--profile-steps", type=int, default=3)
     ap.add_argument("--other-steps", type=int, default=8, help="timed steps of each configuration under other_configs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-others", action="store_true", help="measure only --config")
     ap.add_argument("--others", action="store_true",
                     help="multi-GPU runs measure only the headline unless this is given (then BASELINE.json's DDP configurations 4a / 4b / "
-                         "5 follow it under other_configs); single-GPU runs measure the other configurations by default")
+                         "5 follow it under other_configs); single-GPU --full runs measure the other configurations by default")
     ap.add_argument("--dry-run", action="store_true",
                     help="with --gpus N outside torch.distributed.run: print the child command that would start the ranks (one "
                          "JSON line) and exit without touching a GPU")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.others and not args.full:
+        ap.error("--others measures configurations beyond the headline: give it together with --full")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
+    pin_conv_choices()                                          # in every rank, before the library makes its first choice
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     use_dist = world > 1 or os.environ.get("RG_FORCE_REDUCE") == "1"
@@ -617,7 +726,7 @@ def main():
     head = measure(w, args, dev, rank, world, use_dist, headline=True)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log("cpu baseline (oracle step on %d host threads) ..." % host_cores())
         try:
             cpu = w.cpu_baseline()
@@ -629,7 +738,7 @@ def main():
     others = None
     # N > 1: the headline only, unless --others — the line the driver's scaling curve is computed from must not depend on the graphed
     # configurations (4a, 5) getting through their first multi-rank run (no N > 1 run exists yet: DESIGN section 5)
-    if not args.no_others and args.config == "2" and (world == 1 or args.others):
+    if args.full and not args.no_others and args.config == "2" and (world == 1 or args.others):
         # the other BASELINE configurations, measured in the same process behind the headline.  Multi-GPU: the DDP
         # configurations of BASELINE.json — 4 (the joint trainer: 4a as committed in trainers_b.py:617-814, 4b with FDGANModel
         # in the GAN role) and 5 (dual_gan DPTNModel, fp8) — so that their scaling curves come out of the same runs
