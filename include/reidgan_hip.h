@@ -108,6 +108,17 @@ int rg_conv_set_planes(int mask);
  * of a forward geometry and the tap-reuse-vs-generic path of a 3x3 layer are chosen the same way.  Returns the number of choices
  * measured so far; out[0] / out[1] (int[2], may be NULL): how many kernel choices went to the default kernels / the plane path. */
 int rg_conv_tune_stats(int* out);
+/* development knob (tests): pin one level of the measured choice above.  `kind` is the first field of the choice key as written to
+ * RG_CONV_TUNE_CACHE: 1 / 2 / 4 kernel implementation (fwd / dgrad / wgrad), 16 / 32 tap-reuse vs generic path (fwd / dgrad),
+ * 64 / 128 / 256 tile / split-K plan (fwd / dgrad / wgrad).  index >= 0 pins that kind: every choice of the kind runs candidate
+ * min(index, ncand - 1) at once (before the plane-path mask and RG_CONV_TUNE are consulted), without measuring, synchronising or
+ * recording anything (rg_conv_tune_stats and the cache file are untouched); -1 releases it.  It pins choices, it does not create
+ * them: with RG_CONV_TUNE=0 / RG_CONV_TUNE_PLAN=0 a geometry has one plan and no path choice.  Returns the previous index (-1: not
+ * pinned), or a value below -1 for an unknown kind / an index below -1 (rg_last_error).  Off by default. */
+int rg_conv_set_pick(int kind, int index);
+/* while any kind is pinned, every choice appends one record of 18 ints: the 16 key fields, its candidate count and the index that
+ * ran.  Copies up to max_records records into buf (HOST memory, may be NULL), clears the log and returns how many it held. */
+int rg_conv_pick_log(int* buf, int max_records);
 /* Split-K without the finishing launch.  Registers (count > 0) or removes (counters == NULL) the arrival counters of `stream`:
  * `count` ZERO-INITIALISED 32-bit words of device memory that the caller keeps alive and never writes (the library does not
  * allocate; launches on one stream are ordered and every launch leaves its counters at zero, so one buffer per stream serves all of

@@ -33,10 +33,12 @@
 
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include <array>
 #include <atomic>
 #include <map>
 #include <mutex>
+#include <vector>
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
@@ -2468,12 +2470,51 @@ static void tune_cache_append_locked(const TuneKey& k, int choice) {
     fclose(f);
 }
 
+// rg_conv_set_pick / rg_conv_pick_log (tests): a pinned key kind (the key's first field: 1 / 2 / 4 implementation, 16 / 32 path,
+// 64 / 128 / 256 plan; slot = log2(kind)) runs candidate min(index, ncand - 1) without measuring, synchronising or touching g_tune;
+// while any kind is pinned every choice appends {key[16], ncand, index run} to the log
+static std::atomic<int> g_pick[9] = {{-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}};
+static std::atomic<int> g_pick_pinned{0};
+static std::vector<int> g_pick_records;
+static std::mutex g_pick_mu;
+static const size_t kPickLogMax = 18u << 16;
+static int pick_slot(int kind) {
+    if (kind <= 0 || (kind & (kind - 1)) || kind > 256 || kind == 8) return -1;
+    return __builtin_ctz(kind);
+}
+static void pick_record(const TuneKey& key, int ncand, int choice) {
+    std::lock_guard<std::mutex> lock(g_pick_mu);
+    if (g_pick_records.size() + 18 > kPickLogMax) return;
+    g_pick_records.insert(g_pick_records.end(), key.begin(), key.end());
+    g_pick_records.push_back(ncand);
+    g_pick_records.push_back(choice);
+}
+
+template <typename Run>
+static int choose_impl_measured(int family_bit, const TuneKey& key, hipStream_t stream, int ncand, Run& run);
+
 // run(0): round-3 kernel, run(1): plane path, run(2) (ncand == 3: 128 x 128 tiles only): plane path with EIGHT waves per workgroup
 // (4 x 2 waves of 32 x 64: the staging work per thread halves and four waves per SIMD hide each other's waits; +8 % on the
 // micro-benchmark's 128 x 128 tile).  Each: the kernel launch only; split-K finishers follow.  Returns the implementation that ran
 // LAST (= the chosen one).
 template <typename Run>
 static int choose_impl(int family_bit, const TuneKey& key, hipStream_t stream, int ncand, Run run) {
+    if (g_pick_pinned.load() == 0) return choose_impl_measured(family_bit, key, stream, ncand, run);
+    const int slot = pick_slot(key[0]);
+    const int pin = slot >= 0 ? g_pick[slot].load() : -1;
+    int c;
+    if (pin >= 0) {
+        c = pin < ncand ? pin : ncand - 1;
+        run(c);
+    } else {
+        c = choose_impl_measured(family_bit, key, stream, ncand, run);
+    }
+    pick_record(key, ncand, c);
+    return c;
+}
+
+template <typename Run>
+static int choose_impl_measured(int family_bit, const TuneKey& key, hipStream_t stream, int ncand, Run& run) {
     if (planes_enabled(family_bit)) {
         const int c = (planes_enabled(8) && ncand > 2) ? 2 : 1;
         run(c);
@@ -2860,6 +2901,31 @@ extern "C" int rg_conv_set_planes(int mask) {
     const int old = g_planes_mask < 0 ? (getenv("RG_CONV_PL") ? atoi(getenv("RG_CONV_PL")) : 0) : g_planes_mask;
     g_planes_mask = mask & 15;
     return old;
+}
+
+// development knob (tests/test_conv_candidates_gpu.py): pin the measured choice of one key kind to a candidate index (-1 releases
+// it); returns the previous index, or RG_ERR_INVALID - 1 for an unknown kind / an index below -1
+extern "C" int rg_conv_set_pick(int kind, int index) {
+    const int slot = pick_slot(kind);
+    if (slot < 0 || index < -1) {
+        rg::set_error("rg_conv_set_pick: kind %d / index %d (kinds 1, 2, 4, 16, 32, 64, 128, 256; index >= -1)", kind, index);
+        return RG_ERR_INVALID - 1;
+    }
+    std::lock_guard<std::mutex> lock(g_pick_mu);
+    const int old = g_pick[slot].exchange(index);
+    if ((old >= 0) != (index >= 0)) g_pick_pinned += index >= 0 ? 1 : -1;
+    return old;
+}
+
+// copies up to max_records records of 18 ints (key[16], ncand, index run) logged while a kind was pinned into buf (may be NULL),
+// clears the log and returns how many records it held
+extern "C" int rg_conv_pick_log(int* buf, int max_records) {
+    std::lock_guard<std::mutex> lock(g_pick_mu);
+    const int n = (int)(g_pick_records.size() / 18);
+    const int m = buf ? (n < max_records ? n : (max_records > 0 ? max_records : 0)) : 0;
+    if (m > 0) memcpy(buf, g_pick_records.data(), (size_t)m * 18 * sizeof(int));
+    g_pick_records.clear();
+    return n;
 }
 
 // number of choices the first-call chooser has measured so far (kernel implementation per (family, geometry, plan); tap-reuse vs

@@ -10,9 +10,15 @@ import torch
 from oracle import ref_dualgan as D
 from oracle import ref_fp8 as R
 from tests.golden import cases_dptn as C
-from tests.golden.cases import sub
+from tests.golden.cases import recording_threads, sub
 
 GOLD = np.load(os.path.join(os.path.dirname(__file__), "golden", "reference_dptn.npz"))
+
+
+@pytest.fixture(autouse=True, scope="module")
+def _threads_of_the_recording():
+    with recording_threads():
+        yield
 
 
 def _cmp(got, key, tol=2e-5):

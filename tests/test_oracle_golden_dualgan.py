@@ -3,13 +3,20 @@ dual_gan modules by tests/golden/make_golden_dualgan.py.  No reference and no GP
 import os
 
 import numpy as np
+import pytest
 import torch
 
 from oracle import ref_dualgan as D
 from tests.golden import cases_dualgan as C
-from tests.golden.cases import sub
+from tests.golden.cases import recording_threads, sub
 
 GOLD = np.load(os.path.join(os.path.dirname(__file__), "golden", "reference_dualgan.npz"))
+
+
+@pytest.fixture(autouse=True, scope="module")
+def _threads_of_the_recording():
+    with recording_threads():
+        yield
 
 
 def _cmp(got, key, tol=2e-5):
