@@ -304,6 +304,41 @@ int rg_add_outer_terms(float* m, const float* rowv, const float* colv, float alp
 int rg_segment_mean(const float* x, const void* order, const void* offsets, float* out, int segments, int D,
                     rg_stream_t stream);
 
+/* ---- k-reciprocal re-ranking (Zhong et al., CVPR 2017) behind compute_jaccard_distance, CC/clustercontrast/utils/
+ * faiss_rerank.py:31-127, and re_ranking, CC/clustercontrast/utils/rerank.py:32-99.  The encodings stay sparse: row lists
+ * sets / w [N][cap] with counts [N] before the query expansion, CSR (rowptr [N + 1], cols, vals) and its column lists
+ * (colptr [N + 1], crow, cval) after it; all index arrays int32, N <= 65536.  No floating-point atomics anywhere.
+ *   rg_rerank_expand        rank [N][R] (ascending distance).  R(i, k) = { j in rank[i][:k] : i in rank[j][:k] }; sets[i] =
+ *                           R(i, kf) united with every R(c, kh), c in R(i, kf), that has more than 2/3 of its members in
+ *                           R(i, kf); sorted, unique; counts[i] is the full size (at most kf * (kh + 1); entries beyond cap
+ *                           are dropped, so a count above cap asks for a second call)
+ *   rg_rerank_weights_feat  w[i][e] = softmax_e(-(2 - 2 x_i . x_e)) over the row's set, x [N][D]
+ *   rg_rerank_weights_dist  w[i][e] = exp(-orig[i][e]) / sum_e, orig [N][N]
+ *   rg_rerank_qe_count      local query expansion, row i = mean of the rows rank[i][:k2] (rank NULL: k2 == 1, the row
+ *                           itself): rowcnt[i] = columns of the union, rowptr = their exclusive prefix sum
+ *   rg_rerank_qe_fill       the CSR rows: columns ascending, terms added in rank order, divided by k2
+ *   rg_rerank_columns       column lists of the CSR matrix (cursor: N ints of scratch; order inside a column unspecified)
+ *   rg_rerank_jaccard       out[i][j - col_off] = 1 - m / (2 - m), m = sum_c min(V[i][c], V[j][c]) over row i's columns in
+ *                           ascending order, rows i < rows, columns col_off <= j < N, out [rows][N - col_off]; orig != NULL:
+ *                           (1 - lambda) * that + lambda * orig[i][j]; clamp != 0: negative results become 0.  chunk = columns
+ *                           accumulated per workgroup (<= 16384; 0 = automatic), any value gives the same bits
+ *   rg_rerank_orig_dist     orig = transpose(A^2 / max(A^2, axis 0)), A = [[q_q, q_g], [q_g^T, g_g]] (colmax: N floats of scratch) */
+int rg_rerank_expand(const int* rank, int N, int R, int kf, int kh, int* sets, int* counts, int cap, rg_stream_t stream);
+int rg_rerank_weights_feat(const float* x, int N, int D, const int* sets, const int* counts, int cap, float* w,
+                           rg_stream_t stream);
+int rg_rerank_weights_dist(const float* orig, int N, const int* sets, const int* counts, int cap, float* w, rg_stream_t stream);
+int rg_rerank_qe_count(const int* rank, int R, int k2, int N, const int* sets, const int* counts, int cap, int* rowcnt,
+                       int* rowptr, rg_stream_t stream);
+int rg_rerank_qe_fill(const int* rank, int R, int k2, int N, const int* sets, const float* w, const int* counts, int cap,
+                      const int* rowptr, int* cols, float* vals, rg_stream_t stream);
+int rg_rerank_columns(const int* rowptr, const int* cols, const float* vals, int N, int64_t nnz, int* colptr, int* cursor,
+                      int* crow, float* cval, rg_stream_t stream);
+int rg_rerank_jaccard(const int* rowptr, const int* cols, const float* vals, const int* colptr, const int* crow,
+                      const float* cval, int N, int rows, int col_off, const float* orig, float lambda_value, int clamp,
+                      float* out, int chunk, rg_stream_t stream);
+int rg_rerank_orig_dist(const float* q_g, const float* q_q, const float* g_g, int Q, int G, float* colmax, float* orig,
+                        rg_stream_t stream);
+
 /* ---- conv + frozen-statistics BatchNorm fold (E / D_id of FD-GAN: set_bn_fix, FD/fdgan/networks.py:57-60 with
  * trainable affine parameters, model.py:72-85).  Forward: rg_conv2d_fwd with scale/shift from rg_bn_fold — the
  * pre-normalisation tensor is never written.  Backward without it:

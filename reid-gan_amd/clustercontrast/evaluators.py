@@ -2,9 +2,11 @@
 
 Mirror of the numeric part of CC/clustercontrast/evaluators.py: `extract_cnn_feature` (:16-20), `extract_all_feature`
 (:22-27), `pairwise_distance` (:71-88) (FD/reid/evaluators.py:76-98 and FD/reid/feature_extraction/cnn.py:9-16 are the same
-functions).  The loader loop `extract_features` (:30-68), CMC / mAP scoring, re-ranking and the `Evaluator` class are host
-code and stay the reference's: with its tree behind this one on sys.path they are inherited at the bottom of
-this file and call the functions defined here.
+functions).  The loader loop `extract_features` (:30-68), CMC / mAP scoring and the `Evaluator` class are host code and
+stay the reference's: with its tree behind this one on sys.path they are inherited at the bottom of this
+file and call the functions defined here.  Re-ranking (`Evaluator.evaluate(..., rerank=True)`, :138-142) runs on the
+device: the inherited class imports `re_ranking` from `.utils.rerank`, which resolves to this build's
+clustercontrast/utils/rerank.py.
 """
 from __future__ import print_function, absolute_import
 
@@ -62,7 +64,8 @@ def pairwise_distance(features, query=None, gallery=None):
     return dist_m.cpu(), x.numpy(), y.numpy()
 
 
-# `extract_features`, `Evaluator`, `evaluate_all`, CMC / mAP and re-ranking are the reference's own (CPU) code: when its tree sits behind this
-# one on sys.path they are taken from there, and they call the functions above (rg_hip/overlay.py)
+# `extract_features`, `Evaluator`, `evaluate_all` and CMC / mAP are the reference's own (CPU) code: when its tree sits behind this
+# one on sys.path they are taken from there, and they call the functions above (rg_hip/overlay.py); the `re_ranking` they import
+# is this build's (clustercontrast/utils/rerank.py, on the device)
 from rg_hip.overlay import inherit as _rg_inherit  # noqa: E402
 _rg_inherit(globals())

@@ -1284,6 +1284,155 @@ def segment_mean(x, order, offsets):
     return out
 
 
+# ------------------------------------------------------------------------------------------------
+# k-reciprocal re-ranking (csrc/rerank.hip): sparse encodings as row lists, see include/reidgan_hip.h
+# ------------------------------------------------------------------------------------------------
+def _chk_rr(t, name, dtype=torch.float32, dim=None):
+    """as _chk, but a non-contiguous tensor is refused instead of copied: these arrays index each other by position"""
+    if not torch.is_tensor(t):
+        raise TypeError("rg_hip: %s must be a tensor, got %s" % (name, type(t).__name__))
+    if not t.is_cuda:
+        raise RuntimeError("rg_hip: %s must live on the GPU (got %s); the HIP path has no CPU fallback" % (name, t.device))
+    if t.dtype != dtype:
+        raise TypeError("rg_hip: %s must be %s, got %s" % (name, dtype, t.dtype))
+    if dim is not None and t.dim() != dim:
+        raise ValueError("rg_hip: %s must have %d dimensions, got shape %s" % (name, dim, tuple(t.shape)))
+    if not t.is_contiguous():
+        raise ValueError("rg_hip: %s must be contiguous (shape %s, strides %s)" % (name, tuple(t.shape), t.stride()))
+    if t.device.index != _DEV[0]:
+        _bind_device(t)
+    return t
+
+
+def rerank_expand(rank, kf, kh, cap=None):
+    """(sets int32 [N, cap], counts int32 [N]): expanded k-reciprocal set of every row of the ranking `rank` int32 [N, R]
+    (kf / kh = columns read for the full / the half sets).  The default cap is the worst case kf * (kh + 1), capped at N."""
+    rank = _chk_rr(rank, "rank", torch.int32, 2)
+    N, R = rank.shape
+    kf, kh = int(kf), int(kh)
+    if not (1 <= kh <= kf <= R):
+        raise ValueError("rg_hip: rerank_expand needs 1 <= kh <= kf <= rank.shape[1], got kf=%d kh=%d R=%d" % (kf, kh, R))
+    cap = min(N, kf * (kh + 1)) if cap is None else int(cap)
+    sets = torch.empty((N, cap), dtype=torch.int32, device=rank.device)
+    counts = torch.empty((N,), dtype=torch.int32, device=rank.device)
+    lib.rg_rerank_expand(_p(rank), N, R, kf, kh, _p(sets), _p(counts), cap, _stream())
+    return sets, counts
+
+
+def rerank_weights(sets, counts, x=None, orig=None):
+    """w [N, cap]: softmax of -(2 - 2 x_i . x_e) over each row's set (x [N, D]), or exp(-orig[i, e]) / sum (orig [N, N])"""
+    sets, counts = _chk_rr(sets, "sets", torch.int32, 2), _chk_rr(counts, "counts", torch.int32, 1)
+    if (x is None) == (orig is None):
+        raise ValueError("rg_hip: rerank_weights takes exactly one of x and orig")
+    N, cap = sets.shape
+    w = torch.empty((N, cap), dtype=torch.float32, device=sets.device)      # entries beyond counts[i] are never read
+    if x is not None:
+        x = _chk_rr(x, "x", torch.float32, 2)
+        if x.data_ptr() & 15:            # the kernel reads the gathered rows as 16-byte vectors
+            x = x.clone()
+        if x.shape[0] != N or counts.numel() != N:
+            raise ValueError("rg_hip: rerank_weights: x %s, sets %s, counts %s disagree" % (tuple(x.shape), tuple(sets.shape), tuple(counts.shape)))
+        lib.rg_rerank_weights_feat(_p(x), N, x.shape[1], _p(sets), _p(counts), cap, _p(w), _stream())
+    else:
+        orig = _chk_rr(orig, "orig", torch.float32, 2)
+        if tuple(orig.shape) != (N, N) or counts.numel() != N:
+            raise ValueError("rg_hip: rerank_weights: orig %s must be [%d, %d]" % (tuple(orig.shape), N, N))
+        lib.rg_rerank_weights_dist(_p(orig), N, _p(sets), _p(counts), cap, _p(w), _stream())
+    return w
+
+
+def rerank_query_expand(sets, w, counts, rank=None, k2=1):
+    """CSR (rowptr int32 [N + 1], cols int32 [nnz], vals [nnz]) of the encodings after the local query expansion: row i = mean of
+    the rows rank[i, :k2]; rank None (k2 == 1) keeps every row.  Reads one integer back (nnz) to size the arrays."""
+    sets, counts, w = _chk_rr(sets, "sets", torch.int32, 2), _chk_rr(counts, "counts", torch.int32, 1), _chk_rr(w, "w", torch.float32, 2)
+    N, cap = sets.shape
+    if tuple(w.shape) != (N, cap) or counts.numel() != N:
+        raise ValueError("rg_hip: rerank_query_expand: sets %s, w %s, counts %s disagree" % (tuple(sets.shape), tuple(w.shape), tuple(counts.shape)))
+    k2, R = int(k2), 0
+    if rank is not None:
+        rank = _chk_rr(rank, "rank", torch.int32, 2)
+        R = rank.shape[1]
+        if rank.shape[0] != N or not (1 <= k2 <= min(R, 64)):
+            raise ValueError("rg_hip: rerank_query_expand needs rank [N, R] and 1 <= k2 <= min(R, 64), got %s, k2=%d" % (tuple(rank.shape), k2))
+    elif k2 != 1:
+        raise ValueError("rg_hip: rerank_query_expand without a ranking is the identity (k2 == 1), got k2=%d" % k2)
+    rowcnt = torch.empty((N,), dtype=torch.int32, device=sets.device)
+    rowptr = torch.empty((N + 1,), dtype=torch.int32, device=sets.device)
+    lib.rg_rerank_qe_count(_p(rank), R, k2, N, _p(sets), _p(counts), cap, _p(rowcnt), _p(rowptr), _stream())
+    nnz = int(rowptr[N].item())
+    if nnz <= 0 or nnz >= 2 ** 31:
+        raise RuntimeError("rg_hip: rerank_query_expand: %d non-zeros do not fit the int32 row pointers" % nnz)
+    cols = torch.empty((nnz,), dtype=torch.int32, device=sets.device)
+    vals = torch.empty((nnz,), dtype=torch.float32, device=sets.device)
+    lib.rg_rerank_qe_fill(_p(rank), R, k2, N, _p(sets), _p(w), _p(counts), cap, _p(rowptr), _p(cols), _p(vals), _stream())
+    return rowptr, cols, vals
+
+
+def rerank_columns(rowptr, cols, vals):
+    """column lists (colptr int32 [N + 1], crow int32 [nnz], cval [nnz]) of a CSR matrix; order inside a column unspecified"""
+    rowptr, cols, vals = _chk_rr(rowptr, "rowptr", torch.int32, 1), _chk_rr(cols, "cols", torch.int32, 1), _chk_rr(vals, "vals", torch.float32, 1)
+    N, nnz = rowptr.numel() - 1, cols.numel()
+    if N < 1 or vals.numel() != nnz:
+        raise ValueError("rg_hip: rerank_columns: rowptr %s, cols %s, vals %s disagree" % (tuple(rowptr.shape), tuple(cols.shape), tuple(vals.shape)))
+    colptr = torch.empty((N + 1,), dtype=torch.int32, device=cols.device)
+    cursor = torch.empty((N,), dtype=torch.int32, device=cols.device)
+    crow, cval = torch.empty_like(cols), torch.empty_like(vals)
+    lib.rg_rerank_columns(_p(rowptr), _p(cols), _p(vals), N, nnz, _p(colptr), _p(cursor), _p(crow), _p(cval), _stream())
+    return colptr, crow, cval
+
+
+def rerank_jaccard(csr, csc, rows=None, col_off=0, orig=None, lambda_value=0.0, clamp=True, chunk=0):
+    """[rows, N - col_off] Jaccard distances of the sparse encodings (csr / csc as returned above); with `orig` [N, N]:
+    (1 - lambda) * jaccard + lambda * orig.  chunk = columns accumulated per workgroup, 0 = automatic; same bits either way."""
+    rowptr, cols, vals = csr
+    colptr, crow, cval = csc
+    rowptr, colptr = _chk_rr(rowptr, "rowptr", torch.int32, 1), _chk_rr(colptr, "colptr", torch.int32, 1)
+    cols, crow = _chk_rr(cols, "cols", torch.int32, 1), _chk_rr(crow, "crow", torch.int32, 1)
+    vals, cval = _chk_rr(vals, "vals", torch.float32, 1), _chk_rr(cval, "cval", torch.float32, 1)
+    N = rowptr.numel() - 1
+    rows = N if rows is None else int(rows)
+    col_off, chunk = int(col_off), int(chunk)
+    if colptr.numel() != N + 1 or not (cols.numel() == vals.numel() == crow.numel() == cval.numel()):
+        raise ValueError("rg_hip: rerank_jaccard: row and column lists disagree")
+    if not (1 <= rows <= N and 0 <= col_off < N) or chunk < 0:
+        raise ValueError("rg_hip: rerank_jaccard: rows=%d col_off=%d chunk=%d outside N=%d" % (rows, col_off, chunk, N))
+    if orig is not None:
+        orig = _chk_rr(orig, "orig", torch.float32, 2)
+        if orig.shape[1] != N or orig.shape[0] < rows:
+            raise ValueError("rg_hip: rerank_jaccard: orig %s must be [>= %d, %d]" % (tuple(orig.shape), rows, N))
+    out = torch.empty((rows, N - col_off), dtype=torch.float32, device=cols.device)
+    lib.rg_rerank_jaccard(_p(rowptr), _p(cols), _p(vals), _p(colptr), _p(crow), _p(cval), N, rows, col_off, _p(orig),
+                          float(lambda_value), int(bool(clamp)), _p(out), chunk, _stream())
+    return out
+
+
+def rerank_orig_dist(q_g, q_q, g_g):
+    """transpose(A^2 / max(A^2, axis 0)) [Q + G, Q + G] of A = [[q_q, q_g], [q_g^T, g_g]] (re_ranking's normalised matrix)"""
+    q_g, q_q, g_g = _chk_rr(q_g, "q_g_dist", torch.float32, 2), _chk_rr(q_q, "q_q_dist", torch.float32, 2), _chk_rr(g_g, "g_g_dist", torch.float32, 2)
+    Q, G = q_g.shape
+    if tuple(q_q.shape) != (Q, Q) or tuple(g_g.shape) != (G, G):
+        raise ValueError("rg_hip: rerank_orig_dist: q_g %s needs q_q [%d, %d] and g_g [%d, %d], got %s and %s"
+                         % (tuple(q_g.shape), Q, Q, G, G, tuple(q_q.shape), tuple(g_g.shape)))
+    colmax = torch.empty((Q + G,), dtype=torch.float32, device=q_g.device)
+    orig = torch.empty((Q + G, Q + G), dtype=torch.float32, device=q_g.device)
+    lib.rg_rerank_orig_dist(_p(q_g), _p(q_q), _p(g_g), Q, G, _p(colmax), _p(orig), _stream())
+    return orig
+
+
+def rerank_from_rank(rank, kf, kh, k2, x=None, orig=None, rows=None, col_off=0, lambda_value=0.0, clamp=True, chunk=0, debug=False):
+    """Stages 2-6 of the re-ranking on an initial ranking `rank` int32 [N, R]: expanded k-reciprocal sets, their weights (from
+    the features x or the normalised distances orig), local query expansion over rank[:, :k2], column lists, Jaccard rows.
+    debug=True also returns {"rank", "sets", "counts", "w", "rowptr", "cols", "vals"} (device tensors)."""
+    sets, counts = rerank_expand(rank, kf, kh)
+    w = rerank_weights(sets, counts, x=x) if orig is None else rerank_weights(sets, counts, orig=orig)
+    csr = rerank_query_expand(sets, w, counts, rank=rank if k2 != 1 else None, k2=k2)
+    csc = rerank_columns(*csr)
+    out = rerank_jaccard(csr, csc, rows=rows, col_off=col_off, orig=orig, lambda_value=lambda_value, clamp=clamp, chunk=chunk)
+    if debug:
+        return out, dict(rank=rank, sets=sets, counts=counts, w=w, rowptr=csr[0], cols=csr[1], vals=csr[2])
+    return out
+
+
 def adam_advance(state, beta1, beta2):
     lib.rg_adam_advance(_p(state), beta1, beta2, _stream())
 

@@ -1,5 +1,10 @@
 """SURVEY §8f ranks 1-2 at the reference's sizes: kNN over 12 936 x 2048 features (k = 15) and the 3 368 x 15 913 x 2048
-evaluation distance matrix (Market-1501).  Times exclude the final device->host copies of the results."""
+evaluation distance matrix (Market-1501).  Times exclude the final device->host copies of the results.
+
+`--jaccard N,D,k1,k2 [--noise X]` times compute_jaccard_distance's stages instead (clustered synthetic features, 20 per
+identity, noise X relative to the unit centre, default 0.30; larger noise = less separated identities = longer sets):
+device events around every stage, one warm-up pass, median of `--reps` passes, the device->host copy of the [N, N]
+result separately.  The query expansion reads one integer back (the size of its output), which its time includes."""
 import os, sys, time, json
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "reid-gan_amd"))
@@ -8,6 +13,54 @@ import torch.nn.functional as F
 from rg_hip import ops
 from clustercontrast.evaluators import _dist_block
 dev = torch.device("cuda", 0)
+
+
+def jaccard_mode(spec, reps, noise):
+    import numpy as np
+    from clustercontrast.utils.faiss_rerank import l2_rank, half_k
+    N, D, k1, k2 = (int(v) for v in spec.split(","))
+    g = torch.Generator(device=dev).manual_seed(0)
+    n_id = (N + 19) // 20
+    centres = F.normalize(torch.randn(n_id, D, generator=g, device=dev), dim=1)
+    x = centres.repeat_interleave(20, dim=0)[:N] + noise * torch.randn(N, D, generator=g, device=dev) / D ** 0.5
+    x = F.normalize(x, dim=1)[torch.randperm(N, generator=g, device=dev)].contiguous()
+    kh = min(half_k(k1) + 1, k1)
+    names = ["rank", "expand", "weights", "query_expansion", "columns", "jaccard", "d2h"]
+    host = torch.empty((N, N), dtype=torch.float32).pin_memory()
+    samples = {n: [] for n in names}
+    info = {}
+    for it in range(reps + 1):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(names) + 1)]
+        ev[0].record()
+        rank = l2_rank(x, k1); ev[1].record()
+        sets, counts = ops.rerank_expand(rank, k1, kh); ev[2].record()
+        w = ops.rerank_weights(sets, counts, x=x); ev[3].record()
+        csr = ops.rerank_query_expand(sets, w, counts, rank=rank if k2 != 1 else None, k2=k2); ev[4].record()
+        csc = ops.rerank_columns(*csr); ev[5].record()
+        out = ops.rerank_jaccard(csr, csc, clamp=True); ev[6].record()
+        host.copy_(out); ev[7].record()
+        torch.cuda.synchronize()
+        if it:                                   # pass 0 is the warm-up
+            for i, n in enumerate(names):
+                samples[n].append(ev[i].elapsed_time(ev[i + 1]))
+        info = {"set_mean": round(float(counts.float().mean()), 1), "set_max": int(counts.max()), "nnz": int(csr[1].numel()),
+                "support_mean": round(float((out < 1).sum()) / N, 1)}
+        del rank, sets, counts, w, csr, csc, out
+    med = {n: round(float(np.median(v)), 3) for n, v in samples.items()}
+    res = {"jaccard": {"N": N, "D": D, "k1": k1, "k2": k2, "noise": noise, "reps": reps}, "stage_ms_median": med,
+           "stage_ms_min_max": {n: [round(min(v), 3), round(max(v), 3)] for n, v in samples.items()},
+           "device_total_ms": round(sum(v for n, v in med.items() if n != "d2h"), 3), "d2h_ms": med["d2h"],
+           "result_MB": round(N * N * 4 / 1e6, 1)}
+    res.update(info)
+    print(json.dumps(res))
+
+
+if "--jaccard" in sys.argv:
+    _reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 5
+    _noise = float(sys.argv[sys.argv.index("--noise") + 1]) if "--noise" in sys.argv else 0.30
+    jaccard_mode(sys.argv[sys.argv.index("--jaccard") + 1], _reps, _noise)
+    sys.exit(0)
+
 g = torch.Generator(device=dev).manual_seed(0)
 x = F.normalize(torch.randn(12936, 2048, generator=g, device=dev), dim=1)
 
