@@ -339,6 +339,28 @@ int rg_rerank_jaccard(const int* rowptr, const int* cols, const float* vals, con
 int rg_rerank_orig_dist(const float* q_g, const float* q_q, const float* g_g, int Q, int G, float* colmax, float* orig,
                         rg_stream_t stream);
 
+/* ---- DBSCAN on a precomputed symmetric distance matrix d [N][ld] (fp32, or fp16 with is_half = 1), the pseudo-labelling step
+ * between compute_jaccard_distance and generate_cluster_features (CC/examples/cluster_contrast_train_usl.py:146-200), with
+ * the labels of scikit-learn's DBSCAN(metric='precomputed'): adj[i][j] = d[i][j] <= eps (entries widened to fp32, compared
+ * with the fp32 eps; the diagonal counts like any other entry; a negative entry is simply <= eps), core[i] = |adj[i]| >=
+ * min_samples, clusters = connected components of the core-core graph numbered by ascending lowest core index, a non-core
+ * point gets the lowest cluster number among its core neighbours or -1.  An asymmetric matrix is not reproduced (scikit-learn's
+ * search becomes directed).  All index arrays int32, N <= 65536; integer atomics only, results independent of their order.
+ *   rg_dbscan_count        cnt[i] = entries of row i that are <= eps; rowptr [N + 1] = their exclusive prefix sum
+ *   rg_dbscan_fill         nbr[rowptr[i] .. rowptr[i + 1]) = those columns, ascending; core[i] = cnt[i] >= min_samples
+ *   rg_dbscan_components   parent[i] = lowest core index of i's component for a core point, -1 otherwise (lock-free
+ *                          union-find: the higher root is hooked under the lower by compare-and-swap; every walk descends)
+ *   rg_dbscan_labels       isroot[i] = parent[i] == i, rootnum [N + 1] = its exclusive prefix sum (rootnum[N] = number of
+ *                          clusters), labels int64 [N] as above
+ *   rg_dbscan_asymmetry    *count = entries above the diagonal whose bits differ from their mirror's */
+int rg_dbscan_count(const void* d, int is_half, int N, int64_t ld, float eps, int* cnt, int* rowptr, rg_stream_t stream);
+int rg_dbscan_fill(const void* d, int is_half, int N, int64_t ld, float eps, int min_samples, const int* rowptr, int* nbr, int* core,
+                   rg_stream_t stream);
+int rg_dbscan_components(const int* rowptr, const int* nbr, const int* core, int N, int* parent, rg_stream_t stream);
+int rg_dbscan_labels(const int* rowptr, const int* nbr, const int* parent, int N, int* isroot, int* rootnum, int64_t* labels,
+                     rg_stream_t stream);
+int rg_dbscan_asymmetry(const void* d, int is_half, int N, int64_t ld, int* count, rg_stream_t stream);
+
 /* ---- conv + frozen-statistics BatchNorm fold (E / D_id of FD-GAN: set_bn_fix, FD/fdgan/networks.py:57-60 with
  * trainable affine parameters, model.py:72-85).  Forward: rg_conv2d_fwd with scale/shift from rg_bn_fold — the
  * pre-normalisation tensor is never written.  Backward without it:

@@ -15,6 +15,8 @@ return types, so `rerank_dist = compute_jaccard_distance(features, k1=args.k1, k
 accepted and ignored.  `use_float16=True` makes the reference hold V and the result in float16; here the computation stays
 fp32 and the fp32 result is cast to float16 on return (same dtype as the reference's, closer to the exact values).
 The input is the CPU tensor `extract_features` yields or a device tensor; there is no CPU path.
+`return_device=True` (not in the reference) keeps the result on the device for clustercontrast.utils.dbscan /
+clustercontrast.utils.pseudo_labels, which removes the 669 MB copy per epoch at Market-1501 size.
 """
 from __future__ import absolute_import, print_function
 
@@ -57,11 +59,13 @@ def l2_rank(x, k):
 
 
 def compute_jaccard_distance(target_features, k1=20, k2=6, print_flag=True, search_option=0, use_float16=False, chunk=0,
-                             debug=False):
+                             debug=False, return_device=False):
     """numpy [N, N] float32 (float16 with use_float16: the fp32 result, cast) k-reciprocal Jaccard distance of the rows of
     `target_features` [N, D].  As in the reference the weights treat the rows as L2-normalised (2 - 2 x.y) whatever the
     input is, while the ranking uses the true L2 distance.  `chunk` (columns per workgroup of the Jaccard kernel, 0 =
-    automatic) and `debug` (also return the device-side ranks, sets and encodings) are for tests."""
+    automatic) and `debug` (also return the device-side ranks, sets and encodings) are for tests.  `return_device=True`
+    returns the fp32 [N, N] device tensor instead (whatever `use_float16` says) and copies nothing to the host: the input
+    of clustercontrast.utils.dbscan.DBSCAN."""
     end = time.time()
     if print_flag:
         print('Computing jaccard distance...')
@@ -79,9 +83,12 @@ def compute_jaccard_distance(target_features, k1=20, k2=6, print_flag=True, sear
     rank = l2_rank(x, k1)              # the reference searches k1 neighbours: its slice [:k1+1] has k1 entries
     res = ops.rerank_from_rank(rank, k1, min(half_k(k1) + 1, k1), k2, x=x, clamp=True, chunk=chunk, debug=debug)
     out = res[0] if debug else res
-    jaccard_dist = out.cpu().numpy()
-    if use_float16:
-        jaccard_dist = jaccard_dist.astype(np.float16)
+    if return_device:
+        jaccard_dist = out
+    else:
+        jaccard_dist = out.cpu().numpy()
+        if use_float16:
+            jaccard_dist = jaccard_dist.astype(np.float16)
     if print_flag:
         print("Jaccard distance computing time cost: {}".format(time.time() - end))
     return (jaccard_dist, res[1]) if debug else jaccard_dist

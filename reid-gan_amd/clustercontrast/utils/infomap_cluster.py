@@ -105,6 +105,29 @@ def generate_cluster_features(labels, features):
     return ops.segment_mean(x, torch.tensor(order, dtype=torch.int64).to(dev), torch.tensor(offsets, dtype=torch.int64).to(dev))
 
 
+@torch.no_grad()
+def generate_cluster_features_device(labels, features):
+    """`generate_cluster_features` for int64 labels that already live on the device (ops.dbscan's): the member lists are
+    built there by a stable sort of the non-negative labels, so every cluster is summed in ascending sample index like the
+    host loop above and the centroids equal its result bit for bit.  No label leaves the device; returns a device tensor
+    [number of distinct labels, D]."""
+    if not torch.is_tensor(labels) or not labels.is_cuda or labels.dtype != torch.int64 or labels.dim() != 1:
+        raise TypeError("generate_cluster_features_device: labels must be a 1-D int64 device tensor")
+    x = features if torch.is_tensor(features) else torch.stack(list(features), dim=0)
+    x = x.float().to(labels.device).contiguous()
+    if x.dim() != 2 or x.shape[0] != labels.numel():
+        raise ValueError("generate_cluster_features_device: features %s do not match %d labels" % (tuple(x.shape), labels.numel()))
+    keep = torch.nonzero(labels != -1).flatten()                  # ascending sample index
+    if keep.numel() == 0:
+        raise ValueError("generate_cluster_features_device: every sample is an outlier")
+    sorted_labels, perm = torch.sort(labels[keep], stable=True)
+    order = keep[perm].contiguous()
+    _, sizes = torch.unique_consecutive(sorted_labels, return_counts=True)
+    offsets = torch.zeros(sizes.numel() + 1, dtype=torch.int64, device=labels.device)
+    offsets[1:] = torch.cumsum(sizes, dim=0)
+    return ops.segment_mean(x, order, offsets)
+
+
 def cluster_by_infomap(nbrs, dists, min_sim, cluster_num=2):
     raise NotImplementedError("Infomap community detection is the third-party `infomap` CPU package driven by the "
                               "reference's own cluster_by_infomap (infomap_cluster.py:147-227); it is outside the GPU hot "

@@ -12,27 +12,6 @@ namespace {
 constexpr int kMaxN = 65536;              // LDS bitmaps of the set kernels: 3 * N/8 bytes
 constexpr int kJaccardMaxChunk = 16384;   // fp32 accumulators of one Jaccard workgroup: 64 KB, two workgroups per CU
 
-// exclusive prefix sum over the block (blockDim.x a multiple of 64, <= 1024); `red` holds >= 17 ints; *total = block sum
-__device__ __forceinline__ int block_excl_scan(int v, int* red, int* total) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    __syncthreads();
-    if (lane == 63) red[wid] = inc;
-    __syncthreads();
-    int base = 0, t = 0;
-    for (int w = 0; w < nw; ++w) {
-        if (w < wid) base += red[w];
-        t += red[w];
-    }
-    *total = t;
-    return base + inc - v;
-}
-
 // Turns the LDS bitmap `bits` (words of 32 columns) into the ascending index list out[0 .. min(count, cap)); returns the
 // count.  `wpre` is `words` ints of LDS.
 __device__ __forceinline__ int emit_bitmap(const unsigned* bits, int words, int* wpre, int* red, int* out, int cap) {
@@ -242,22 +221,6 @@ __global__ __launch_bounds__(256) void rerank_qe_kernel(const int* __restrict__ 
     }
 }
 
-// ptr[0 .. n] = exclusive prefix sum of cnt[0 .. n), one workgroup
-__global__ __launch_bounds__(1024) void rerank_scan_kernel(const int* __restrict__ cnt, int n, int* __restrict__ ptr) {
-    __shared__ int red[17];
-    const int per = (n + 1023) / 1024, t0 = threadIdx.x * per, t1 = min(n, t0 + per);
-    int s = 0;
-    for (int t = t0; t < t1; ++t) s += cnt[t];
-    int total;
-    int run = block_excl_scan(s, red, &total);
-    for (int t = t0; t < t1; ++t) {
-        const int c = cnt[t];
-        ptr[t] = run;
-        run += c;
-    }
-    if (threadIdx.x == 0) ptr[n] = total;
-}
-
 __global__ void rerank_col_count_kernel(const int* __restrict__ cols, int64_t nnz, int* __restrict__ colcnt) {
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < nnz; p += (int64_t)gridDim.x * blockDim.x)
         atomicAdd(&colcnt[cols[p]], 1);
@@ -423,7 +386,7 @@ extern "C" int rg_rerank_qe_count(const int* rank, int R, int k2, int N, const i
     rg::ProfScope prof(rg::FAM_CM, stream, 0.0, 0.0);
     hipLaunchKernelGGL(rerank_qe_kernel<false>, dim3(N), dim3(256), sizeof(int) * 2 * (size_t)words, stream, rank, R, k2, N, sets,
                        (const float*)nullptr, counts, cap, rowcnt, (const int*)nullptr, (int*)nullptr, (float*)nullptr);
-    hipLaunchKernelGGL(rerank_scan_kernel, dim3(1), dim3(1024), 0, stream, rowcnt, N, rowptr);
+    hipLaunchKernelGGL(rg_scan_kernel<1024>, dim3(1), dim3(1024), 0, stream, rowcnt, N, rowptr);
     return rg::check_launch("rg_rerank_qe_count");
 }
 
@@ -450,7 +413,7 @@ extern "C" int rg_rerank_columns(const int* rowptr, const int* cols, const float
     int64_t g = rg::cdiv64(nnz, 256);
     if (g > 4096) g = 4096;
     hipLaunchKernelGGL(rerank_col_count_kernel, dim3((unsigned)g), dim3(256), 0, stream, cols, (int64_t)nnz, cursor);
-    hipLaunchKernelGGL(rerank_scan_kernel, dim3(1), dim3(1024), 0, stream, cursor, N, colptr);
+    hipLaunchKernelGGL(rg_scan_kernel<1024>, dim3(1), dim3(1024), 0, stream, cursor, N, colptr);
     if (hipMemcpyAsync(cursor, colptr, sizeof(int) * (size_t)N, hipMemcpyDeviceToDevice, stream) != hipSuccess) {
         rg::set_error("rg_rerank_columns: hipMemcpyAsync failed");
         return RG_ERR_LAUNCH;

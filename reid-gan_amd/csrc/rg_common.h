@@ -114,6 +114,45 @@ __device__ __forceinline__ float rg_block_max(float v, float* red) {
     return t;
 }
 
+// exclusive prefix sum over the block (blockDim.x a multiple of 64, <= 1024); `red` holds >= 17 ints; *total = block sum
+__device__ __forceinline__ int block_excl_scan(int v, int* red, int* total) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int o = __shfl_up(inc, off, 64);
+        if (lane >= off) inc += o;
+    }
+    __syncthreads();
+    if (lane == 63) red[wid] = inc;
+    __syncthreads();
+    int base = 0, t = 0;
+    for (int w = 0; w < nw; ++w) {
+        if (w < wid) base += red[w];
+        t += red[w];
+    }
+    *total = t;
+    return base + inc - v;
+}
+
+// ptr[0 .. n] = exclusive prefix sum of cnt[0 .. n), one workgroup of kThreads (a template, so that only the translation
+// units that launch it carry a copy)
+template <int kThreads>
+__global__ __launch_bounds__(kThreads) void rg_scan_kernel(const int* __restrict__ cnt, int n, int* __restrict__ ptr) {
+    __shared__ int red[17];
+    const int per = (n + kThreads - 1) / kThreads, t0 = threadIdx.x * per, t1 = min(n, t0 + per);
+    int s = 0;
+    for (int t = t0; t < t1; ++t) s += cnt[t];
+    int total;
+    int run = block_excl_scan(s, red, &total);
+    for (int t = t0; t < t1; ++t) {
+        const int c = cnt[t];
+        ptr[t] = run;
+        run += c;
+    }
+    if (threadIdx.x == 0) ptr[n] = total;
+}
+
 // activation codes shared by conv epilogues and the element-wise kernels
 #define RG_ACT_NONE 0
 #define RG_ACT_RELU 1

@@ -4,7 +4,15 @@ evaluation distance matrix (Market-1501).  Times exclude the final device->host 
 `--jaccard N,D,k1,k2 [--noise X]` times compute_jaccard_distance's stages instead (clustered synthetic features, 20 per
 identity, noise X relative to the unit centre, default 0.30; larger noise = less separated identities = longer sets):
 device events around every stage, one warm-up pass, median of `--reps` passes, the device->host copy of the [N, N]
-result separately.  The query expansion reads one integer back (the size of its output), which its time includes."""
+result separately.  The query expansion reads one integer back (the size of its output), which its time includes.
+
+`--dbscan N,D,k1,k2[,eps] [--noise X]` times the DBSCAN pseudo-labelling that follows on the same kind of input (eps 0.6,
+min_samples 4 as the training script): device events around `count` (row counts + their prefix sum, first pass over the
+matrix; the read-back of nnz is charged to it), `fill` (second pass), `components`, `labels` (with the read-back of the
+cluster count) and `centroids`; a device-to-device copy of the matrix in the same run as the bandwidth yardstick of the two
+passes; the wall time of `dbscan_pseudo_labels` end to end (Jaccard + DBSCAN + centroids + the N labels to the host); and
+the path it replaces on the same matrix and box: the device->host copy, sklearn.cluster.DBSCAN(n_jobs=-1).fit_predict and
+the host-loop generate_cluster_features, on the host clock (skipped with a note when scikit-learn is absent)."""
 import os, sys, time, json
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "reid-gan_amd"))
@@ -54,6 +62,93 @@ def jaccard_mode(spec, reps, noise):
     res.update(info)
     print(json.dumps(res))
 
+
+def _clustered_features(N, D, noise):
+    g = torch.Generator(device=dev).manual_seed(0)
+    n_id = (N + 19) // 20
+    centres = F.normalize(torch.randn(n_id, D, generator=g, device=dev), dim=1)
+    x = centres.repeat_interleave(20, dim=0)[:N] + noise * torch.randn(N, D, generator=g, device=dev) / D ** 0.5
+    return F.normalize(x, dim=1)[torch.randperm(N, generator=g, device=dev)].contiguous()
+
+
+def dbscan_mode(spec, reps, noise):
+    import numpy as np
+    from clustercontrast.utils.faiss_rerank import compute_jaccard_distance
+    from clustercontrast.utils.infomap_cluster import generate_cluster_features, generate_cluster_features_device
+    from clustercontrast.utils.pseudo_labels import dbscan_pseudo_labels
+    parts = spec.split(",")
+    N, D, k1, k2 = (int(v) for v in parts[:4])
+    eps, min_samples = (float(parts[4]) if len(parts) > 4 else 0.6), 4
+    x = _clustered_features(N, D, noise)
+    J = compute_jaccard_distance(x, k1=k1, k2=k2, print_flag=False, return_device=True)
+    names = ["count", "fill", "components", "labels", "centroids", "d2d_copy"]
+    samples = {n: [] for n in names}
+    info = {}
+    for it in range(reps + 1):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(names) + 1)]
+        twin = torch.empty_like(J)
+        ev[0].record()
+        cnt, rowptr = ops.dbscan_count(J, eps)
+        nnz = int(rowptr[N].item()); ev[1].record()
+        nbr, core = ops.dbscan_fill(J, eps, min_samples, rowptr, nnz); ev[2].record()
+        parent = ops.dbscan_components(rowptr, nbr, core); ev[3].record()
+        labels, n_clusters = ops.dbscan_labels(rowptr, nbr, core, parent); ev[4].record()
+        cents = generate_cluster_features_device(labels, x) if n_clusters else None; ev[5].record()
+        twin.copy_(J); ev[6].record()
+        torch.cuda.synchronize()
+        if it:                                   # pass 0 is the warm-up
+            for i, n in enumerate(names):
+                samples[n].append(ev[i].elapsed_time(ev[i + 1]))
+        info = {"nnz": nnz, "row_mean": round(nnz / N, 1), "n_clusters": n_clusters, "outliers": int((labels < 0).sum()),
+                "core_points": int(core.sum())}
+        del cnt, rowptr, nbr, core, parent, cents, twin
+    med = {n: round(float(np.median(v)), 3) for n, v in samples.items()}
+    new_total = round(sum(v for n, v in med.items() if n != "d2d_copy"), 3)
+    mb = N * N * 4 / 1e6
+    wall = []
+    for it in range(reps + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        got, _, _ = dbscan_pseudo_labels(x, k1=k1, k2=k2, eps=eps, min_samples=min_samples)
+        torch.cuda.synchronize()
+        if it:
+            wall.append((time.perf_counter() - t0) * 1e3)
+    res = {"dbscan": {"N": N, "D": D, "k1": k1, "k2": k2, "eps": eps, "min_samples": min_samples, "noise": noise, "reps": reps},
+           "stage_ms_median": med, "stage_ms_min_max": {n: [round(min(v), 3), round(max(v), 3)] for n, v in samples.items()},
+           "dbscan_device_total_ms": new_total, "matrix_MB": round(mb, 1),
+           "count_GBps": round(mb / med["count"], 1), "fill_GBps": round(mb / med["fill"], 1),
+           "d2d_copy_read_GBps": round(mb / med["d2d_copy"], 1),
+           "pseudo_labels_end_to_end_wall_ms": round(float(np.median(wall)), 3)}
+    res.update(info)
+    host = torch.empty((N, N), dtype=torch.float32).pin_memory()
+    t0 = time.perf_counter()
+    host.copy_(J)
+    torch.cuda.synchronize()
+    t_copy = (time.perf_counter() - t0) * 1e3
+    try:
+        from sklearn.cluster import DBSCAN as SkDBSCAN
+    except ImportError:
+        res["host_path"] = {"d2h_ms": round(t_copy, 1), "note": "scikit-learn is not installed here: sklearn DBSCAN not timed"}
+    else:
+        Jh = host.numpy()
+        t0 = time.perf_counter()
+        want = SkDBSCAN(eps=eps, min_samples=min_samples, metric="precomputed", n_jobs=-1).fit_predict(Jh)
+        t_sk = (time.perf_counter() - t0) * 1e3
+        t0 = time.perf_counter()
+        if (want >= 0).any():
+            generate_cluster_features(want, x)
+        torch.cuda.synchronize()
+        t_cf = (time.perf_counter() - t0) * 1e3
+        res["host_path"] = {"d2h_ms": round(t_copy, 1), "sklearn_dbscan_ms": round(t_sk, 1), "host_loop_centroids_ms": round(t_cf, 1),
+                            "total_ms": round(t_copy + t_sk + t_cf, 1), "labels_equal": bool(np.array_equal(want, got))}
+    print(json.dumps(res))
+
+
+if "--dbscan" in sys.argv:
+    _reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 5
+    _noise = float(sys.argv[sys.argv.index("--noise") + 1]) if "--noise" in sys.argv else 0.30
+    dbscan_mode(sys.argv[sys.argv.index("--dbscan") + 1], _reps, _noise)
+    sys.exit(0)
 
 if "--jaccard" in sys.argv:
     _reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 5
