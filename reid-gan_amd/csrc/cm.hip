@@ -9,7 +9,7 @@
 // reduction for each norm.  No atomics, bit-reproducible, independent of dispatch order.
 //
 // The (B x D)·(D x K) logits GEMM and its dgrad run on the MFMA implicit-GEMM kernels
-// (conv_igemm.hip with 1x1 geometry); see the host code.
+// (conv_fwd.hip with 1x1 geometry); see the host code.
 #include "rg_common.h"
 
 namespace {

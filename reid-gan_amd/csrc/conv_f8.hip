@@ -771,13 +771,13 @@ static int pad16(int v) { return (v + 15) / 16 * 16; }
 
 // RG_F8_BM=64|128 pins the tile height of the forward / data-gradient GEMMs (A/B measurements); anything else is ignored
 static int f8_bm_override() {
-    static const int v = getenv("RG_F8_BM") ? atoi(getenv("RG_F8_BM")) : 0;
+    static const int v = rg::env_int("RG_F8_BM", 0);
     return (v == 64 || v == 128) ? v : 0;
 }
 
 // RG_F8_NB=2 selects the register-staged two-buffer loop (the first version; kept for A/B measurements), default the 4-deep DMA ring
 static int f8_ring() {
-    static const int nb = getenv("RG_F8_NB") ? atoi(getenv("RG_F8_NB")) : 4;
+    static const int nb = rg::env_int("RG_F8_NB", 4);
     return nb == 2 ? 2 : 4;
 }
 #define RG_F8_LAUNCH(MODE_, GRID_)                      \

@@ -1,4 +1,5 @@
-// bf16-plane operand tiles for the split-bf16 convolution kernels (included by conv_igemm.hip inside its anonymous namespace).
+// bf16-plane operand tiles for the split-bf16 convolution kernels (included by conv_fwd.hip, conv_dgrad.hip and conv_wgrad.hip inside
+// their anonymous namespaces; RG_PLANES_FWD / RG_PLANES_DGRAD / RG_PLANES_WGRAD select the section a unit launches).
 //
 // Round-3 kernels kept the LDS operand tiles in fp32 and every wave split every fragment it read into its three bf16 pieces
 // (9 VALU instructions per element pair, per reading wave): 230 VALU instructions beside 24 MFMAs per 16-deep k-tile, VALU-bound.
@@ -18,6 +19,7 @@
 #pragma once
 #include "conv_planes_core.h"
 
+#ifdef RG_PLANES_FWD
 // ---------------------------------------------------------------------------------------------
 // forward.  Same loaders, split-K and epilogues as conv_fwd_kernel; BMODE 0 generic gather (order (c, r, s)), 1: (r, s)-major
 // over the [K][RS][C] filter copy, 2: 1x1 / stride 1 / pad 0 with float4 pixel loads.
@@ -228,7 +230,9 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_fwd_pl_kernel(const ConvP p
     });
     store_tile_nchw<T>(p, acc, m0, n0, wm, wn, lane, p.Ng, p.P * p.Q, p.d_pq, split);
 }
+#endif  // RG_PLANES_FWD
 
+#ifdef RG_PLANES_DGRAD
 // ---------------------------------------------------------------------------------------------
 // data gradient (and the forward of ConvTranspose2d): conv_dgrad_kernel's loaders, classes, split-K and epilogues.
 // MODE 0: filters [K][C][KH][KW] by scalar loads (thread = input channel, EA consecutive reduction indices) -> PL_R;
@@ -430,7 +434,9 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_dgrad_pl_kernel(const Dgrad
     }
     store_tile_epilogue_any<T>(p, acc, ob, (unsigned)HW * 4u, mrow0, (cl.poff + nt) * WN + wn);
 }
+#endif  // RG_PLANES_DGRAD
 
+#ifdef RG_PLANES_WGRAD
 // ---------------------------------------------------------------------------------------------
 // weight gradient: conv_wgrad_kernel's split mapping, loaders and partial-tile store.  The reduction runs over output pixels, so
 // both operands are "k-contiguous" where they vectorise (dy rows; x rows of a 1x1 layer or shifted float4s of a stride-1 filter
@@ -644,3 +650,4 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_wgrad_pl_kernel(const ConvP
             }
     }
 }
+#endif  // RG_PLANES_WGRAD

@@ -1,5 +1,5 @@
 // Core of the bf16-plane operand path (layouts, split-and-store chunks, the MFMA k-step, the k-loop): see conv_planes.h for the
-// design notes.  Depends only on the arithmetic typedefs of conv_igemm.hip (floatx16, int4r, Split3, split3_pair, mfma_bf16,
+// design notes.  Depends only on the arithmetic typedefs of conv_core.h (floatx16, int4r, Split3, split3_pair, mfma_bf16,
 // RG_PIN), so tools/micro/gemm_pl_bench.hip can include it on its own.
 #pragma once
 

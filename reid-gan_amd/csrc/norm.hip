@@ -1342,7 +1342,7 @@ extern "C" int rg_rows_sum_pair(const float* a, const float* b, float* out_a, fl
 // Train-mode BatchNorm, one launch per direction (see the kernels): rg_bn_train_fused_ok says whether the geometry qualifies;
 // otherwise use rg_bn_stats + rg_bn_apply_fwd / rg_bn_bwd_reduce + rg_bn_bwd_apply.
 // development switch: RG_BN_REG=0 keeps the loop kernels (A/B timing)
-static const bool g_bn_reg = !(getenv("RG_BN_REG") && atoi(getenv("RG_BN_REG")) == 0);
+static const bool g_bn_reg = rg::env_int("RG_BN_REG", 1) != 0;
 
 extern "C" size_t rg_bn_train_fused_ok(int N, int C, int HW) {
     return (int64_t)N * HW <= 16384 && C >= 128 ? 1 : 0;

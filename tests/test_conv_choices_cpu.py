@@ -1,5 +1,6 @@
 """CPU: profiles/conv_choices_mi355x.txt — the measured conv choices the bench pins (RG_CONV_TUNE_CACHE) — stays consistent with
-the candidate lists of csrc/conv_igemm.hip.  A line is the 16-field choice key and the index of the candidate that won; an index
+the candidate lists of the conv library (plans: csrc/conv_igemm.hip; kernel implementations and paths: csrc/conv_fwd.hip,
+conv_dgrad.hip, conv_wgrad.hip).  A line is the 16-field choice key and the index of the candidate that won; an index
 the library cannot have produced would be clamped or re-measured silently, and the bench would no longer time fixed kernels."""
 import os
 

@@ -12,14 +12,17 @@ CONV = "conv"            # fp32 implicit-GEMM family (FAM_CONV_FWD / _DGRAD / _W
 CONV_F8 = "conv_f8"
 
 FAMILY = {
-    # conv_igemm.hip
-    "conv_fwd_kernel": CONV, "conv_dgrad_kernel": CONV, "conv_wgrad_kernel": CONV, "conv3x3_halo_kernel": CONV,
-    "conv1x1_dma_kernel": CONV, "wgrad1x1_dma_kernel": CONV, "splitk_reduce_fold_kernel": CONV, "conv_splitk_finish_strided_kernel": CONV,
-    "conv_fwd_pl_kernel": CONV, "conv_dgrad_pl_kernel": CONV, "conv_wgrad_pl_kernel": CONV,      # conv_planes.h
-    "conv_dgrad_smallc_kernel": CONV, "conv_dgrad_smallc_px_kernel": CONV, "conv_fwd_k1_kernel": CONV,
-    "conv_wgrad_k1_kernel": CONV, "conv_splitk_finish_kernel": CONV, "splitk_reduce_kernel": CONV,
-    "conv_splitk_finish_vec_kernel": CONV, "splitk_reduce_vec_kernel": CONV, "conv_wgrad_k1_px4_kernel": CONV,
-    "weights_to_krsc_kernel": CONV, "weights_to_krsc_multi_kernel": CONV, "weights_to_ck_kernel": CONV,
+    # conv_fwd.hip
+    "conv_fwd_kernel": CONV, "conv_fwd_k1_kernel": CONV,
+    # conv_dgrad.hip
+    "conv_dgrad_kernel": CONV, "conv1x1_dma_kernel": CONV, "conv_dgrad_smallc_kernel": CONV, "conv_dgrad_smallc_px_kernel": CONV,
+    "conv_splitk_finish_strided_kernel": CONV,
+    # conv_wgrad.hip
+    "conv_wgrad_kernel": CONV, "conv_wgrad_k1_kernel": CONV, "conv_wgrad_k1_px4_kernel": CONV, "splitk_reduce_kernel": CONV,
+    "splitk_reduce_vec_kernel": CONV, "splitk_reduce_fold_kernel": CONV, "weights_to_krsc_kernel": CONV, "weights_to_krsc_multi_kernel": CONV,
+    # conv_halo.h, conv_finish.h, conv_planes.h (instantiated by the units above)
+    "conv3x3_halo_kernel": CONV, "conv_splitk_finish_kernel": CONV, "conv_splitk_finish_vec_kernel": CONV,
+    "conv_fwd_pl_kernel": CONV, "conv_dgrad_pl_kernel": CONV, "conv_wgrad_pl_kernel": CONV,
     # norm.hip: conv helpers of the folded (frozen-statistics) BatchNorm
     "bn_fold_wgrad_kernel": CONV, "fold_filters_multi_kernel": CONV, "bn_fold_kernel": CONV,
     # conv_f8.hip

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel register / spill / LDS summary of one HIP source (hipcc -Rpass-analysis=kernel-resource-usage, no GPU needed).
-usage: kernel_resources.py reid-gan_amd/csrc/conv_igemm.hip [extra hipcc flags]"""
+usage: kernel_resources.py reid-gan_amd/csrc/conv_fwd.hip [extra hipcc flags]     (conv_dgrad.hip, conv_wgrad.hip, ...)"""
 import re
 import subprocess
 import sys

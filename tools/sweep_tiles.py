@@ -1,5 +1,5 @@
 """For every conv geometry of the FD-GAN step: the planner's choice vs every forced (tile, split-K) choice, fwd and dgrad
-(development aid for the cost model in conv_igemm.hip:plan_gemm).  usage: sweep_tiles.py N [resnet|gan]"""
+(development aid for the cost model in csrc/conv_igemm.hip:plan_gemm / plan_candidates).  usage: sweep_tiles.py N [resnet|gan]"""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "reid-gan_amd"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
