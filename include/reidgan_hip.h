@@ -361,6 +361,23 @@ int rg_dbscan_labels(const int* rowptr, const int* nbr, const int* parent, int N
                      rg_stream_t stream);
 int rg_dbscan_asymmetry(const void* d, int is_half, int N, int64_t ld, int* count, rg_stream_t stream);
 
+/* ---- CMC / mAP scoring of a query x gallery distance matrix dist [Q][ld] (fp32, or fp64 with is_double = 1; compared in its
+ * own type), CC/clustercontrast/evaluation_metrics/ranking.py `cmc` / `mean_ap`, without a sort.  All id / camera arrays int32.
+ * Per query i: valid_j = (gid_j != qid_i) | (gcam_j != qcam_i) (and gcam_j != qcam_i with separate_camera_set), pos_j = valid_j
+ * & (gid_j == qid_i);
+ *   npos[i]            positives (0: the query is skipped)
+ *   ap[i]     fp64     (1 / P) sum_p TP_le(p) / N_le(p): positives / valid entries with d <= d_p, ties by value (-0.0 == 0.0,
+ *                      +-inf ordinary values) = scikit-learn's average_precision_score; the terms are added as 64.64 fixed point
+ *   first[i]           valid non-matching entries before the first positive in stable (d, j) order (-1 without a positive)
+ *   hits[i][0:topk]    hits[i][r] = positives with exactly r valid non-matching entries before them in stable order
+ * and over the queries, in a fixed order: counts [topk + 2] = {status, valid queries, histogram of first}, sums [topk + 1] =
+ * {sum_i ap[i], sum_i hits[i][k] / npos[i]}.  status != 0: a row holds a NaN (the results are then unspecified, nothing is
+ * written out of bounds).  chunk = positives held in LDS per pass over a row (1 .. 1024; 0 = automatic); rows with more take
+ * further passes, any value gives the same bits.  Integer atomics only. */
+int rg_rank_eval(const void* dist, int is_double, int Q, int G, int64_t ld, const int* query_ids, const int* gallery_ids,
+                 const int* query_cams, const int* gallery_cams, int separate_camera_set, int topk, int chunk, int* npos, double* ap,
+                 int* first, int* hits, int* counts, double* sums, rg_stream_t stream);
+
 /* ---- conv + frozen-statistics BatchNorm fold (E / D_id of FD-GAN: set_bn_fix, FD/fdgan/networks.py:57-60 with
  * trainable affine parameters, model.py:72-85).  Forward: rg_conv2d_fwd with scale/shift from rg_bn_fold — the
  * pre-normalisation tensor is never written.  Backward without it:

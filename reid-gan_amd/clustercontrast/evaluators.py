@@ -2,11 +2,12 @@
 
 Mirror of the numeric part of CC/clustercontrast/evaluators.py: `extract_cnn_feature` (:16-20), `extract_all_feature`
 (:22-27), `pairwise_distance` (:71-88) (FD/reid/evaluators.py:76-98 and FD/reid/feature_extraction/cnn.py:9-16 are the same
-functions).  The loader loop `extract_features` (:30-68), CMC / mAP scoring and the `Evaluator` class are host code and
-stay the reference's: with its tree behind this one on sys.path they are inherited at the bottom of this
-file and call the functions defined here.  Re-ranking (`Evaluator.evaluate(..., rerank=True)`, :138-142) runs on the
-device: the inherited class imports `re_ranking` from `.utils.rerank`, which resolves to this build's
-clustercontrast/utils/rerank.py.
+functions).  The loader loop `extract_features` (:30-68), `evaluate_all` and the `Evaluator` class keep the reference's names
+only when its tree sits behind this one on sys.path: they are inherited at the bottom of this file, call the functions defined
+here, and import `cmc` / `mean_ap` from this build's `.evaluation_metrics` (scored on the device) and `re_ranking` from this
+build's `.utils.rerank`.  Their device-resident counterparts live here under names of their own — `extract_features_device`,
+`evaluate_all_device`, `DeviceEvaluator` — and need no reference tree: features, distance matrices and the re-ranked matrix stay
+on the device and one `ops.rank_eval` call scores mAP and the `market1501` CMC.
 """
 from __future__ import print_function, absolute_import
 
@@ -47,13 +48,15 @@ def _dist_block(x, y, xx_scale, with_y_norm):
     return ops.add_outer_terms(d, rowv=ops.row_sqsum(x), colv=None, alpha=1.0, a=xx_scale)
 
 
-def pairwise_distance(features, query=None, gallery=None):
+def pairwise_distance(features, query=None, gallery=None, return_device=False):
+    """return_device=True: the distance matrix (and, with query / gallery, the two feature blocks) stay device tensors"""
     dev = _device()
     if query is None and gallery is None:
         n = len(features)
         x = torch.cat(list(features.values())).view(n, -1).float().to(dev).contiguous()
         # 2 |x_i|^2 - 2 x_i . x_j  (the reference's expression for the self-distance matrix, :71-77)
-        return _dist_block(x, x, 2.0, False).cpu()
+        d = _dist_block(x, x, 2.0, False)
+        return d if return_device else d.cpu()
     x = torch.cat([features[f].unsqueeze(0) for f, _, _ in query], 0)
     y = torch.cat([features[f].unsqueeze(0) for f, _, _ in gallery], 0)
     m, n = x.size(0), y.size(0)
@@ -61,11 +64,123 @@ def pairwise_distance(features, query=None, gallery=None):
     y = y.view(n, -1)
     xd, yd = x.float().to(dev).contiguous(), y.float().to(dev).contiguous()
     dist_m = _dist_block(xd, yd, 1.0, True)
+    if return_device:
+        return dist_m, xd, yd
     return dist_m.cpu(), x.numpy(), y.numpy()
 
 
-# `extract_features`, `Evaluator`, `evaluate_all` and CMC / mAP are the reference's own (CPU) code: when its tree sits behind this
-# one on sys.path they are taken from there, and they call the functions above (rg_hip/overlay.py); the `re_ranking` they import
-# is this build's (clustercontrast/utils/rerank.py, on the device)
+class DeviceFeatures(object):
+    """What `extract_features_device` returns: all features as one [N, D] device tensor plus fname -> row.  `features[fname]`
+    is a row view, so the object also serves where the reference's OrderedDict of features is read."""
+
+    def __init__(self, matrix, index):
+        self.matrix, self.index = matrix, index
+
+    def __getitem__(self, fname):
+        return self.matrix[self.index[fname]]
+
+    def __len__(self):
+        return len(self.index)
+
+    def rows(self, entries):
+        """[len(entries), D] device block of the (fname, pid, cam) triples, one gather"""
+        idx = torch.as_tensor([self.index[f] for f, _, _ in entries], dtype=torch.int64).to(self.matrix.device)
+        return self.matrix.index_select(0, idx).view(len(entries), -1).float().contiguous()
+
+
+def extract_features_device(model, data_loader, print_freq=50):
+    """The reference's `extract_features` loop (:30-68) with the features kept on the device: (DeviceFeatures, labels)."""
+    import time
+    from collections import OrderedDict
+    from .utils.meters import AverageMeter
+    model.eval()
+    batch_time, data_time = AverageMeter(), AverageMeter()
+    blocks, index, labels = [], OrderedDict(), OrderedDict()
+    dev = _device()
+    end = time.time()
+    with torch.no_grad():
+        for i, (imgs, fnames, pids, _, _) in enumerate(data_loader):
+            data_time.update(time.time() - end)
+            outputs = model(_to_torch(imgs).to(dev, non_blocking=True)).data
+            base = sum(b.shape[0] for b in blocks)
+            blocks.append(outputs.reshape(outputs.shape[0], -1))
+            for k, (fname, pid) in enumerate(zip(fnames, pids)):
+                index[fname] = base + k
+                labels[fname] = pid
+            batch_time.update(time.time() - end)
+            end = time.time()
+            if (i + 1) % print_freq == 0:
+                print('Extract Features: [{}/{}]\t'
+                      'Time {:.3f} ({:.3f})\t'
+                      'Data {:.3f} ({:.3f})\t'
+                      .format(i + 1, len(data_loader),
+                              batch_time.val, batch_time.avg,
+                              data_time.val, data_time.avg))
+    return DeviceFeatures(torch.cat(blocks, 0), index), labels
+
+
+def pairwise_distance_device(features, query, gallery):
+    """[len(query), len(gallery)] squared distances of a DeviceFeatures, on the device"""
+    return _dist_block(features.rows(query), features.rows(gallery), 1.0, True)
+
+
+def evaluate_all_device(distmat, query=None, gallery=None,
+                        query_ids=None, gallery_ids=None,
+                        query_cams=None, gallery_cams=None,
+                        cmc_topk=(1, 5, 10), cmc_flag=False):
+    """The reference's `evaluate_all` (:91-122, without its two unused feature arguments) from one `ops.rank_eval` call: mAP and
+    the `market1501` CMC (first match, cameras not separated) come out of the same pass over the matrix.  Same printed lines
+    and return values."""
+    import numpy as np
+    from .evaluation_metrics import ranking as R
+    if query is not None and gallery is not None:
+        query_ids = [pid for _, pid, _ in query]
+        gallery_ids = [pid for _, pid, _ in gallery]
+        query_cams = [cam for _, _, cam in query]
+        gallery_cams = [cam for _, _, cam in gallery]
+    else:
+        assert (query_ids is not None and gallery_ids is not None
+                and query_cams is not None and gallery_cams is not None)
+    res = R._score(distmat, query_ids, gallery_ids, query_cams, gallery_cams, 100, False)
+    mAP = float(res["ap_sum"] / res["num_valid"])
+    print('Mean AP: {:4.1%}'.format(mAP))
+
+    if (not cmc_flag):
+        return mAP
+
+    scores = res["first_hist"].astype(np.float64).cumsum() / res["num_valid"]
+    print('CMC Scores:')
+    for k in cmc_topk:
+        print('  top-{:<4}{:12.1%}'.format(k, scores[k - 1]))
+    return scores, mAP
+
+
+class DeviceEvaluator(object):
+    """The reference's `Evaluator` (:125-142) with the features, the distance matrices and the re-ranked matrix kept on the
+    device; works with no reference tree."""
+
+    def __init__(self, model):
+        super(DeviceEvaluator, self).__init__()
+        self.model = model
+
+    def evaluate(self, data_loader, query, gallery, cmc_flag=False, rerank=False):
+        from .utils.rerank import re_ranking
+        features, _ = extract_features_device(self.model, data_loader)
+        distmat = pairwise_distance_device(features, query, gallery)
+        results = evaluate_all_device(distmat, query=query, gallery=gallery, cmc_flag=cmc_flag)
+
+        if (not rerank):
+            return results
+
+        print('Applying person re-ranking ...')
+        distmat_qq = pairwise_distance_device(features, query, query)
+        distmat_gg = pairwise_distance_device(features, gallery, gallery)
+        distmat = re_ranking(distmat, distmat_qq, distmat_gg, return_device=True)
+        return evaluate_all_device(distmat, query=query, gallery=gallery, cmc_flag=cmc_flag)
+
+
+# `extract_features`, `Evaluator` and `evaluate_all` are the reference's own host code: when its tree sits behind this one on
+# sys.path they are taken from there, and they call the functions above (rg_hip/overlay.py); the `re_ranking`, `cmc` and `mean_ap`
+# they import are this build's (clustercontrast/utils/rerank.py, clustercontrast/evaluation_metrics/, on the device)
 from rg_hip.overlay import inherit as _rg_inherit  # noqa: E402
 _rg_inherit(globals())

@@ -38,8 +38,9 @@ def _as_f32(a, name):
     return t.detach().float()
 
 
-def re_ranking(q_g_dist, q_q_dist, g_g_dist, k1=20, k2=6, lambda_value=0.3, chunk=0, debug=False):
-    """numpy [Q, G] float32: (1 - lambda) * Jaccard distance + lambda * normalised original distance"""
+def re_ranking(q_g_dist, q_q_dist, g_g_dist, k1=20, k2=6, lambda_value=0.3, chunk=0, debug=False, return_device=False):
+    """numpy [Q, G] float32: (1 - lambda) * Jaccard distance + lambda * normalised original distance
+    (return_device=True: the same matrix as a device tensor, not copied to the host)"""
     q_g, q_q, g_g = _as_f32(q_g_dist, "q_g_dist"), _as_f32(q_q_dist, "q_q_dist"), _as_f32(g_g_dist, "g_g_dist")
     Q, G = q_g.shape
     if tuple(q_q.shape) != (Q, Q) or tuple(g_g.shape) != (G, G):
@@ -62,5 +63,5 @@ def re_ranking(q_g_dist, q_q_dist, g_g_dist, k1=20, k2=6, lambda_value=0.3, chun
     res = ops.rerank_from_rank(rank, k1 + 1, half_k(k1) + 1, k2, orig=orig, rows=Q, col_off=Q, lambda_value=lambda_value,
                                clamp=False, chunk=chunk, debug=debug)
     out = res[0] if debug else res
-    final_dist = out.cpu().numpy()
+    final_dist = out if return_device else out.cpu().numpy()
     return (final_dist, res[1]) if debug else final_dist

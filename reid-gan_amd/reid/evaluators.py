@@ -2,8 +2,8 @@
 
 Mirror of the numeric part of FD-GAN-master/reid/evaluators.py: `pairwise_distance` (:76-98), `extract_embeddings`
 (:19-43) and `CascadeEvaluator` (:183-227, what `baseline.py:103-104` — BASELINE config 1 — calls).  The loader loop
-`extract_features`, `evaluate_all` and the CMC / mAP metrics are host code and stay the reference's (inherited at the bottom of
-this file when its tree sits behind this one on sys.path).
+`extract_features` and `evaluate_all` are host code and stay the reference's (inherited at the bottom of this file when its tree
+sits behind this one on sys.path); the `cmc` / `mean_ap` they import are this build's (reid/evaluation_metrics/, on the device).
 
 MI355X-first restatement of the second stage: the reference scores one query at a time (one embedding-network call on a
 [1, 2048] probe against its top-k gallery rows, 3 368 calls for Market-1501).  Here the first-stage ranking is a device
@@ -114,6 +114,7 @@ class CascadeEvaluator(object):
         return evaluate_all(distmat, query, gallery, dataset=dataset, top1=top1)                # noqa: F821
 
 
-# `extract_features`, `evaluate_all`, `Evaluator`, CMC / mAP are the reference's own host code (rg_hip/overlay.py)
+# `extract_features`, `evaluate_all`, `Evaluator` are the reference's own host code (rg_hip/overlay.py); they score through this
+# build's reid.evaluation_metrics
 from rg_hip.overlay import inherit as _rg_inherit  # noqa: E402
 _rg_inherit(globals())

@@ -1545,6 +1545,55 @@ def dbscan(d, eps, min_samples, debug=False):
     return labels, n_clusters
 
 
+# ------------------------------------------------------------------------------------------------
+# CMC / mAP scoring of a query x gallery distance matrix (csrc/rank_eval.hip)
+# ------------------------------------------------------------------------------------------------
+def rank_eval(dist, query_ids, gallery_ids, query_cams, gallery_cams, topk=100, separate_camera_set=False, chunk=0, debug=False):
+    """Scores the ranking every row of dist [Q, G] (fp32 or fp64, on the device) defines, without sorting it:
+    {"status", "num_valid", "ap_sum", "first_hist" int64 [topk], "allshots" fp64 [topk]} — the number of queries with a
+    positive, the sum of their average precisions, the histogram of the first-match rank and sum_i hits[i, k] / npos[i]
+    (cumsum / num_valid of the last two are the reference's `market1501` and `allshots` CMC curves, ap_sum / num_valid its
+    mAP).  ids / cams are int32 device vectors.  Two small tensors (topk + 2 and topk + 1 numbers) are read back.  A NaN in
+    the matrix raises ValueError.  chunk = positives per pass held in LDS (0 = automatic), same bits for any value.
+    debug=True adds the per-query device tensors "npos", "ap", "first", "hits"."""
+    if not torch.is_tensor(dist) or dist.dtype not in (torch.float32, torch.float64):
+        raise TypeError("rg_hip: rank_eval: dist must be an fp32 or fp64 tensor, got %s"
+                        % (dist.dtype if torch.is_tensor(dist) else type(dist).__name__))
+    dist = _chk_rr(dist, "dist", dist.dtype, 2)
+    Q, G = dist.shape
+    topk, chunk = int(topk), int(chunk)
+    if Q < 1 or G < 1:
+        raise ValueError("rg_hip: rank_eval: dist must be a non-empty [Q, G] matrix, got shape %s" % (tuple(dist.shape),))
+    if topk < 1 or Q * topk >= 2 ** 31:
+        raise ValueError("rg_hip: rank_eval needs topk >= 1 and Q * topk < 2^31, got Q=%d topk=%d" % (Q, topk))
+    if not 0 <= chunk <= 1024:
+        raise ValueError("rg_hip: rank_eval: chunk must be 0 (automatic) or 1 .. 1024, got %d" % chunk)
+    vecs = []
+    for t, name, n in ((query_ids, "query_ids", Q), (gallery_ids, "gallery_ids", G), (query_cams, "query_cams", Q),
+                       (gallery_cams, "gallery_cams", G)):
+        t = _chk_rr(t, name, torch.int32, 1)
+        if t.numel() != n:
+            raise ValueError("rg_hip: rank_eval: %s has %d entries, dist %s needs %d" % (name, t.numel(), tuple(dist.shape), n))
+        vecs.append(t)
+    dev = dist.device
+    npos = torch.empty((Q,), dtype=torch.int32, device=dev)
+    ap = torch.empty((Q,), dtype=torch.float64, device=dev)
+    first = torch.empty((Q,), dtype=torch.int32, device=dev)
+    hits = torch.empty((Q, topk), dtype=torch.int32, device=dev)
+    counts = torch.empty((topk + 2,), dtype=torch.int32, device=dev)
+    sums = torch.empty((topk + 1,), dtype=torch.float64, device=dev)
+    lib.rg_rank_eval(_p(dist), int(dist.dtype == torch.float64), Q, G, G, _p(vecs[0]), _p(vecs[1]), _p(vecs[2]), _p(vecs[3]),
+                     int(bool(separate_camera_set)), topk, chunk, _p(npos), _p(ap), _p(first), _p(hits), _p(counts), _p(sums), _stream())
+    counts_h, sums_h = counts.cpu().numpy(), sums.cpu().numpy()
+    if counts_h[0] != 0:
+        raise ValueError("rg_hip: rank_eval: the distance matrix holds a NaN")
+    res = dict(status=int(counts_h[0]), num_valid=int(counts_h[1]), ap_sum=float(sums_h[0]),
+               first_hist=counts_h[2:].astype("int64"), allshots=sums_h[1:].copy())
+    if debug:
+        res.update(npos=npos, ap=ap, first=first, hits=hits)
+    return res
+
+
 def adam_advance(state, beta1, beta2):
     lib.rg_adam_advance(_p(state), beta1, beta2, _stream())
 

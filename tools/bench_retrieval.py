@@ -12,7 +12,14 @@ matrix; the read-back of nnz is charged to it), `fill` (second pass), `component
 cluster count) and `centroids`; a device-to-device copy of the matrix in the same run as the bandwidth yardstick of the two
 passes; the wall time of `dbscan_pseudo_labels` end to end (Jaccard + DBSCAN + centroids + the N labels to the host); and
 the path it replaces on the same matrix and box: the device->host copy, sklearn.cluster.DBSCAN(n_jobs=-1).fit_predict and
-the host-loop generate_cluster_features, on the host clock (skipped with a note when scikit-learn is absent)."""
+the host-loop generate_cluster_features, on the host clock (skipped with a note when scikit-learn is absent).
+
+`--evaluate [Q,G] [--noise X]` (default 3368,15913: Market-1501's query and gallery sizes; 751 identities, 6 cameras, noise
+0.90) times the CMC / mAP scoring of a [Q, G] distance matrix: device events around `rg_rank_eval` on the fp32 matrix and on
+its fp64 copy (both kernels and the clearing of the outputs) and around a device-to-device copy of the fp32 matrix as the
+bandwidth yardstick, one warm-up pass, median of `--reps`; the wall time of `ops.rank_eval` with its read-back; and, in the
+same run, the host path it replaces: the device->host copy plus the numpy model (tests/rank_eval_hostmodel.py: a stable
+argsort and one scikit-learn `average_precision_score` call per query, what the reference does twice per evaluation)."""
 import os, sys, time, json
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "reid-gan_amd"))
@@ -143,6 +150,86 @@ def dbscan_mode(spec, reps, noise):
                             "total_ms": round(t_copy + t_sk + t_cf, 1), "labels_equal": bool(np.array_equal(want, got))}
     print(json.dumps(res))
 
+
+def evaluate_mode(spec, reps, noise):
+    import numpy as np
+    from rg_hip.lib import lib
+    from clustercontrast.evaluation_metrics import cmc, mean_ap
+    sys.path.insert(0, REPO)
+    from tests import rank_eval_hostmodel as M
+    Q, G = (int(v) for v in spec.split(","))
+    D, n_id, n_cam, topk = 128, 751, 6, 100
+    g = torch.Generator(device=dev).manual_seed(0)
+    centres = F.normalize(torch.randn(n_id, D, generator=g, device=dev), dim=1)
+    ids = torch.randint(0, n_id, (Q + G,), generator=g, device=dev)
+    cams = torch.randint(0, n_cam, (Q + G,), generator=g, device=dev).int()
+    x = F.normalize(centres[ids] + noise * torch.randn(Q + G, D, generator=g, device=dev) / D ** 0.5, dim=1)
+    ids = ids.int()
+    qid, gid, qcam, gcam = ids[:Q].contiguous(), ids[Q:].contiguous(), cams[:Q].contiguous(), cams[Q:].contiguous()
+    dist = _dist_block(x[:Q].contiguous(), x[Q:].contiguous(), 1.0, True)
+    out = dict(npos=torch.empty(Q, dtype=torch.int32, device=dev), ap=torch.empty(Q, dtype=torch.float64, device=dev),
+               first=torch.empty(Q, dtype=torch.int32, device=dev), hits=torch.empty((Q, topk), dtype=torch.int32, device=dev),
+               counts=torch.empty(topk + 2, dtype=torch.int32, device=dev), sums=torch.empty(topk + 1, dtype=torch.float64, device=dev))
+    twin = torch.empty_like(dist)
+    dist64 = dist.double()
+    names = ["rank_eval_fp32", "rank_eval_fp64", "d2d_copy"]
+    samples = {n: [] for n in names}
+    p = ops._p
+    for it in range(reps + 1):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(names) + 1)]
+        ev[0].record()
+        for k, d in enumerate((dist, dist64)):
+            lib.rg_rank_eval(p(d), k, Q, G, G, p(qid), p(gid), p(qcam), p(gcam), 0, topk, 0, p(out["npos"]), p(out["ap"]), p(out["first"]),
+                             p(out["hits"]), p(out["counts"]), p(out["sums"]), ops._stream())
+            ev[k + 1].record()
+        twin.copy_(dist); ev[3].record()
+        torch.cuda.synchronize()
+        if it:                                   # pass 0 is the warm-up
+            for i, n in enumerate(names):
+                samples[n].append(ev[i].elapsed_time(ev[i + 1]))
+    med = {n: round(float(np.median(v)), 3) for n, v in samples.items()}
+    wall = []
+    for it in range(reps + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = ops.rank_eval(dist, qid, gid, qcam, gcam, topk=topk)
+        if it:
+            wall.append((time.perf_counter() - t0) * 1e3)
+    mAP = res["ap_sum"] / res["num_valid"]
+    top1 = float(res["first_hist"][0]) / res["num_valid"]
+    mb = Q * G * 4 / 1e6
+    npos = out["npos"]
+    res = {"evaluate": {"Q": Q, "G": G, "D": D, "identities": n_id, "cameras": n_cam, "topk": topk, "noise": noise, "reps": reps},
+           "stage_ms_median": med, "stage_ms_min_max": {n: [round(min(v), 3), round(max(v), 3)] for n, v in samples.items()},
+           "matrix_MB": round(mb, 1), "rank_eval_fp32_GBps": round(mb / med["rank_eval_fp32"], 1),
+           "rank_eval_fp64_GBps": round(2 * mb / med["rank_eval_fp64"], 1), "d2d_copy_read_GBps": round(mb / med["d2d_copy"], 1),
+           "rank_eval_with_readback_wall_ms": round(float(np.median(wall)), 3), "readback_numbers": 2 * topk + 3,
+           "positives_mean": round(float(npos.float().mean()), 1), "positives_max": int(npos.max()),
+           "valid_queries": int((npos > 0).sum()), "mAP": round(mAP, 6), "top1": round(top1, 6)}
+    # the path it replaces on the same matrix and box: the copy to the host, then a stable argsort and one scikit-learn call per query
+    host = torch.empty((Q, G), dtype=torch.float32).pin_memory()
+    t0 = time.perf_counter()
+    host.copy_(dist)
+    torch.cuda.synchronize()
+    t_copy = (time.perf_counter() - t0) * 1e3
+    hid = [v.cpu().numpy() for v in (qid, gid, qcam, gcam)]
+    t0 = time.perf_counter()
+    want = M.summarize(*M.per_query(host.numpy(), *hid, topk=topk))
+    t_model = (time.perf_counter() - t0) * 1e3
+    res["host_path"] = {"d2h_ms": round(t_copy, 1), "argsort_and_sklearn_loop_ms": round(t_model, 1), "total_ms": round(t_copy + t_model, 1),
+                        "mAP_abs_diff": float(abs(want[0] - mAP)), "top1_equal": bool(want[1][0] == top1),
+                        "cmc_equal": bool(np.array_equal(want[1], cmc(dist, qid, gid, qcam, gcam, topk=topk, first_match_break=True))),
+                        "mean_ap_abs_diff": float(abs(want[0] - mean_ap(dist, qid, gid, qcam, gcam)))}
+    print(json.dumps(res))
+
+
+if "--evaluate" in sys.argv:
+    _i = sys.argv.index("--evaluate") + 1
+    _spec = sys.argv[_i] if _i < len(sys.argv) and not sys.argv[_i].startswith("--") else "3368,15913"
+    _reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 5
+    _noise = float(sys.argv[sys.argv.index("--noise") + 1]) if "--noise" in sys.argv else 0.90
+    evaluate_mode(_spec, _reps, _noise)
+    sys.exit(0)
 
 if "--dbscan" in sys.argv:
     _reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 5

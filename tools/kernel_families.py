@@ -71,6 +71,8 @@ FAMILY = {
     # dbscan.hip
     "dbscan_row_kernel": "misc", "dbscan_parent_init_kernel": "misc", "dbscan_hook_kernel": "misc", "dbscan_flatten_kernel": "misc",
     "dbscan_root_flag_kernel": "misc", "dbscan_label_kernel": "misc", "dbscan_asym_kernel": "misc",
+    # rank_eval.hip
+    "rank_eval_row_kernel": "misc", "rank_eval_reduce_kernel": "misc",
 }
 
 
