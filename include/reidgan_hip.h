@@ -176,6 +176,27 @@ int rg_channel_sum(const float* dy, float* out, int N, int C, int HW, rg_stream_
 /* out_a[c] = sum_n a[n][c], out_b[c] = sum_n b[n][c]: dgamma / dbeta of an affine InstanceNorm2d (torch.nn.InstanceNorm2d
  * backward as used by CC/dual_gan/models/base_function.py:38-49) from the per-(n,c) sums of rg_bn_bwd_reduce. */
 int rg_rows_sum_pair(const float* a, const float* b, float* out_a, float* out_b, int N, int C, rg_stream_t stream);
+/* The IBN layer of the IBN-a ResNets (CC/clustercontrast/models/resnet_ibn_a.py:54-68: split -> InstanceNorm2d(half, affine) on
+ * channels [0, half), BatchNorm2d(C - half) on [half, C) -> cat) on ONE x[N][C][HW] tensor, without the slice copies and the
+ * concatenation: y / dx are the only tensors of the activation's size that are written.
+ *   forward   y = act(affine(xhat)), act = none or ReLU; `residual` must be NULL (bn1 of a Bottleneck has none).  in_mean / in_invstd
+ *             [N*half] are always written.  train != 0: batch statistics for the BN half (biased variance), bn_mean / bn_invstd
+ *             [C-half] written, running_mean / running_var (may be NULL) updated with torch's rule; train == 0: the running statistics
+ *             normalise and nothing is updated (bn_mean / bn_invstd unused).
+ *   backward  dx [N][C][HW] and the four affine gradients; y_act is the forward output (needed when act != none).  bn_mean / bn_stat are
+ *             the saved batch mean / invstd (train, with the batch-statistics correction terms) or the running mean / VARIANCE (eval).
+ * Launches: eval 1 forward, 1 + 1 small backward; train with N*HW <= 16384 the same (one workgroup per BN channel next to the IN lane
+ * groups in one grid); larger extents slice partial + finalize for the BN half, then one launch over all C channels.  Deterministic
+ * (fixed summation order, no atomics).  workspace: rg_ibn_workspace bytes. */
+int64_t rg_ibn_workspace(int N, int C, int HW, int half);
+int rg_ibn_fwd(const float* x, const float* in_gamma, const float* in_beta, const float* bn_gamma, const float* bn_beta,
+               const float* residual, float* y, float* in_mean, float* in_invstd, float* bn_mean, float* bn_invstd,
+               float* running_mean, float* running_var, int N, int C, int HW, int half, int train, float in_eps, float bn_eps,
+               float momentum, int act, void* workspace, size_t workspace_bytes, rg_stream_t stream);
+int rg_ibn_bwd(const float* x, const float* dy, const float* y_act, const float* in_mean, const float* in_invstd,
+               const float* bn_mean, const float* bn_stat, const float* in_gamma, const float* bn_gamma, float* dx,
+               float* d_in_gamma, float* d_in_beta, float* d_bn_gamma, float* d_bn_beta, int N, int C, int HW, int half, int train,
+               float bn_eps, int act, void* workspace, size_t workspace_bytes, rg_stream_t stream);
 int rg_bn_bwd_apply(const float* x, const float* dy, const float* y_act, const float* mean, const float* stat,
                     const float* gamma, const float* sum_dy, const float* sum_dy_xhat, float* dx, float* dres, int N,
                     int C, int HW, int train, int stat_is_var, float eps, int act, float slope, rg_stream_t stream);

@@ -1,5 +1,6 @@
-"""Model registry — mirrors CC/clustercontrast/models/__init__.py:6-59 for the ResNet family (the IBN / two-branch /
-multi-part variants registered there are outside the hot path)."""
+"""Model registry — mirrors CC/clustercontrast/models/__init__.py:6-59 for the ResNet family and the IBN-a ResNets (the
+encoder of the reference's published cluster-contrast recipe); the two-branch (bip / bipd), multi-part (mp) and dsbn variants
+registered there are outside the hot path, SURVEY §2 row 20."""
 from __future__ import absolute_import
 
 from rg_hip.overlay import extend as _rg_extend  # noqa: E402
@@ -8,6 +9,8 @@ _rg_extend(globals(), run_init=False)       # see rg_hip/overlay.py: the referen
 
 from .resnet import *  # noqa: F401,F403
 from .resnet import resnet18, resnet34, resnet50, resnet101, resnet152
+from .resnet_ibn import *  # noqa: F401,F403
+from .resnet_ibn import resnet_ibn50a, resnet_ibn101a
 
 __factory = {
     'resnet18': resnet18,
@@ -15,6 +18,8 @@ __factory = {
     'resnet50': resnet50,
     'resnet101': resnet101,
     'resnet152': resnet152,
+    'resnet_ibn50a': resnet_ibn50a,
+    'resnet_ibn101a': resnet_ibn101a,
 }
 
 

@@ -29,11 +29,7 @@ class ResNet(RGModule):
         self.pretrained = pretrained
         self.depth = depth
         self.cut_at_pooling = cut_at_pooling
-        if depth not in ResNet._depths:
-            raise KeyError("Unsupported depth:", depth)
-        resnet = TVResNet(depth)
-        if pretrained:
-            load_pretrained(resnet, depth)
+        resnet = self._build_trunk(depth, pretrained)
         resnet.layer4[0].conv2.stride = (1, 1)
         resnet.layer4[0].downsample[0].stride = (1, 1)
         self.base = rnn.Sequential(resnet.conv1, resnet.bn1, resnet.relu, resnet.maxpool,
@@ -66,6 +62,16 @@ class ResNet(RGModule):
 
         if not pretrained:
             self.reset_params()
+
+    _returns_map = True        # train mode with num_classes == 0 returns (bn_x, normalised feature map); ResNetIBN: bn_x alone
+
+    def _build_trunk(self, depth, pretrained):
+        if depth not in self._depths:
+            raise KeyError("Unsupported depth:", depth)
+        resnet = TVResNet(depth)
+        if pretrained:
+            load_pretrained(resnet, depth)
+        return resnet
 
     def forward(self, x, test_all=False):
         self._test_all = bool(test_all)
@@ -101,6 +107,9 @@ class ResNet(RGModule):
             out = self.classifier.tf(tape, bn_x)
             tape.push(tuple(mode) + (None, fmap.shape))
             return out
+        if not self._returns_map:
+            tape.push(tuple(mode) + (None, fmap.shape))
+            return bn_x
         gan, gnorm = self._normalize_map(fmap)
         tape.push(tuple(mode) + ((gan, gnorm), fmap.shape))
         return bn_x, gan

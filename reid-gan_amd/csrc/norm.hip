@@ -810,14 +810,15 @@ __device__ __forceinline__ float bn_block_sum(float v, float* red) {
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-__global__ __launch_bounds__(256) void bn_train_fwd_fused_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                                 const float* __restrict__ beta, const float* __restrict__ res,
-                                                                 float* __restrict__ y, float* __restrict__ mean_out,
-                                                                 float* __restrict__ invstd_out, float* __restrict__ running_mean,
-                                                                 float* __restrict__ running_var, int N, int C, int HW, float eps,
-                                                                 float momentum, int act, float slope) {
-    __shared__ float red[4];
-    const int c = blockIdx.x, t = threadIdx.x;
+// `c` is the channel of the tensor, `sc` the index of its statistics / affine parameters (the same number for a BatchNorm; the
+// channel-split IBN layer below normalises channels [half, C) with parameters [0, C - half))
+__device__ __forceinline__ void bn_channel_fwd(const float* __restrict__ x, const float* __restrict__ gamma,
+                                               const float* __restrict__ beta, const float* __restrict__ res,
+                                               float* __restrict__ y, float* __restrict__ mean_out,
+                                               float* __restrict__ invstd_out, float* __restrict__ running_mean,
+                                               float* __restrict__ running_var, int N, int C, int HW, float eps,
+                                               float momentum, int act, float slope, int c, int sc, float* red) {
+    const int t = threadIdx.x;
     const bool vec = (HW & 3) == 0;
     const int rl = vec ? HW >> 2 : HW;                   // units (float4 or float) per row
     const int total = N * rl;
@@ -852,13 +853,13 @@ __global__ __launch_bounds__(256) void bn_train_fwd_fused_kernel(const float* __
     const float var = m2 / cnt;
     const float is = rsqrtf(var + eps);
     if (t == 0) {
-        mean_out[c] = mu;
-        invstd_out[c] = is;
-        if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mu;
-        if (running_var) running_var[c] = (1.f - momentum) * running_var[c] + momentum * (cnt > 1.f ? m2 / (cnt - 1.f) : var);
+        mean_out[sc] = mu;
+        invstd_out[sc] = is;
+        if (running_mean) running_mean[sc] = (1.f - momentum) * running_mean[sc] + momentum * mu;
+        if (running_var) running_var[sc] = (1.f - momentum) * running_var[sc] + momentum * (cnt > 1.f ? m2 / (cnt - 1.f) : var);
     }
-    const float gs = (gamma ? gamma[c] : 1.f) * is;
-    const float sh = (beta ? beta[c] : 0.f) - mu * gs;
+    const float gs = (gamma ? gamma[sc] : 1.f) * is;
+    const float sh = (beta ? beta[sc] : 0.f) - mu * gs;
     for (int i = t; i < total; i += 256) {
         const int n = i / rl, v = i - n * rl;
         const int64_t off = (int64_t)n * cs + (int64_t)c * HW;
@@ -879,6 +880,17 @@ __global__ __launch_bounds__(256) void bn_train_fwd_fused_kernel(const float* __
             y[off + v] = rg_apply_act(o, act, slope);
         }
     }
+}
+
+__global__ __launch_bounds__(256) void bn_train_fwd_fused_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                                 const float* __restrict__ beta, const float* __restrict__ res,
+                                                                 float* __restrict__ y, float* __restrict__ mean_out,
+                                                                 float* __restrict__ invstd_out, float* __restrict__ running_mean,
+                                                                 float* __restrict__ running_var, int N, int C, int HW, float eps,
+                                                                 float momentum, int act, float slope) {
+    __shared__ float red[4];
+    bn_channel_fwd(x, gamma, beta, res, y, mean_out, invstd_out, running_mean, running_var, N, C, HW, eps, momentum, act, slope,
+                   (int)blockIdx.x, (int)blockIdx.x, red);
 }
 
 // ---- the same two kernels for maps whose rows are float4 multiples, with the loads taken out of the loops ---------------------------
@@ -1212,20 +1224,19 @@ static int bn_reg_units(int N, int C, int HW) {
 }
 
 // g = dy * act'(y); sum_dy[c] = sum g, sum_dy_xhat[c] = sum g * xhat; dx = gamma * invstd * (g - mean(g) - xhat * mean(g xhat)); dres = g
-__global__ __launch_bounds__(256) void bn_train_bwd_fused_kernel(const float* __restrict__ x, const float* __restrict__ dy,
-                                                                 const float* __restrict__ yact, const float* __restrict__ mean,
-                                                                 const float* __restrict__ invstd, const float* __restrict__ gamma,
-                                                                 float* __restrict__ dx, float* __restrict__ dres,
-                                                                 float* __restrict__ sum_dy, float* __restrict__ sum_dy_xhat, int N,
-                                                                 int C, int HW, int act, float slope) {
-    __shared__ float red[4];
-    const int c = blockIdx.x, t = threadIdx.x;
+__device__ __forceinline__ void bn_channel_bwd(const float* __restrict__ x, const float* __restrict__ dy,
+                                               const float* __restrict__ yact, const float* __restrict__ mean,
+                                               const float* __restrict__ invstd, const float* __restrict__ gamma,
+                                               float* __restrict__ dx, float* __restrict__ dres,
+                                               float* __restrict__ sum_dy, float* __restrict__ sum_dy_xhat, int N,
+                                               int C, int HW, int act, float slope, int c, int sc, float* red) {
+    const int t = threadIdx.x;
     const bool vec = (HW & 3) == 0;
     const int rl = vec ? HW >> 2 : HW;
     const int total = N * rl;
     const int64_t cs = (int64_t)C * HW;
     const float cnt = (float)N * (float)HW;
-    const float mu = mean[c], is = invstd[c];
+    const float mu = mean[sc], is = invstd[sc];
     const bool has_act = act != RG_ACT_NONE;
     float s1 = 0.f, s2 = 0.f;
     for (int i = t; i < total; i += 256) {
@@ -1251,11 +1262,11 @@ __global__ __launch_bounds__(256) void bn_train_bwd_fused_kernel(const float* __
     s1 = bn_block_sum(s1, red);
     s2 = bn_block_sum(s2, red) * is;
     if (t == 0) {
-        sum_dy[c] = s1;
-        sum_dy_xhat[c] = s2;
+        sum_dy[sc] = s1;
+        sum_dy_xhat[sc] = s2;
     }
     if (!dx && !dres) return;
-    const float gs = (gamma ? gamma[c] : 1.f) * is;
+    const float gs = (gamma ? gamma[sc] : 1.f) * is;
     const float a0 = s1 / cnt, b0 = s2 / cnt * is;
     for (int i = t; i < total; i += 256) {
         const int n = i / rl, v = i - n * rl;
@@ -1284,10 +1295,23 @@ __global__ __launch_bounds__(256) void bn_train_bwd_fused_kernel(const float* __
     }
 }
 
+__global__ __launch_bounds__(256) void bn_train_bwd_fused_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+                                                                 const float* __restrict__ yact, const float* __restrict__ mean,
+                                                                 const float* __restrict__ invstd, const float* __restrict__ gamma,
+                                                                 float* __restrict__ dx, float* __restrict__ dres,
+                                                                 float* __restrict__ sum_dy, float* __restrict__ sum_dy_xhat, int N,
+                                                                 int C, int HW, int act, float slope) {
+    __shared__ float red[4];
+    bn_channel_bwd(x, dy, yact, mean, invstd, gamma, dx, dres, sum_dy, sum_dy_xhat, N, C, HW, act, slope, (int)blockIdx.x,
+                   (int)blockIdx.x, red);
+}
+
 // out_a[c] = sum_n a[n][c], out_b[c] = sum_n b[n][c] (fixed summation order): the affine gradients of an InstanceNorm from the per-(n,c) sums
 // its backward reduction already produced.  Either pair may be NULL.
+// Columns [split, C) go to oa2 / ob2 (the BatchNorm half of an IBN layer); split = C: one output pair.
 __global__ __launch_bounds__(256) void rows_sum_pair_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                            float* __restrict__ oa, float* __restrict__ ob, int N, int C) {
+                                                            float* __restrict__ oa, float* __restrict__ ob, int N, int C,
+                                                            int split, float* __restrict__ oa2, float* __restrict__ ob2) {
     // 16 channels x 16 row lanes per workgroup: lane ny sums rows ny, ny + 16, ...; the 16 lane sums are added in lane order
     __shared__ float sa[16][17], sb[16][17];
     const int cx = threadIdx.x & 15, ny = threadIdx.x >> 4;
@@ -1309,8 +1333,13 @@ __global__ __launch_bounds__(256) void rows_sum_pair_kernel(const float* __restr
             ta += sa[i][cx];
             tb += sb[i][cx];
         }
-        if (a) oa[c] = ta;
-        if (b) ob[c] = tb;
+        if (c < split) {
+            if (a) oa[c] = ta;
+            if (b) ob[c] = tb;
+        } else {
+            if (a) oa2[c - split] = ta;
+            if (b) ob2[c - split] = tb;
+        }
     }
 }
 
@@ -1335,7 +1364,8 @@ extern "C" int rg_rows_sum_pair(const float* a, const float* b, float* out_a, fl
                                 hipStream_t stream) {
     RG_REQUIRE((a || b) && (!a || out_a) && (!b || out_b) && N > 0 && C > 0, "rg_rows_sum_pair: bad arguments");
     rg::ProfScope prof(rg::FAM_NORM, stream, 0.0, 4.0 * ((a ? 1 : 0) + (b ? 1 : 0)) * (double)(N + 1) * C);
-    hipLaunchKernelGGL(rows_sum_pair_kernel, dim3(rg::cdiv(C, 16)), dim3(256), 0, stream, a, b, out_a, out_b, N, C);
+    hipLaunchKernelGGL(rows_sum_pair_kernel, dim3(rg::cdiv(C, 16)), dim3(256), 0, stream, a, b, out_a, out_b, N, C,
+                       C, nullptr, nullptr);
     return rg::check_launch("rg_rows_sum_pair");
 }
 
@@ -1607,3 +1637,496 @@ extern "C" int rg_fold_filters_multi(const void* table, int n_pairs, int total_b
 }
 
 extern "C" int rg_fold_chunk(void) { return FOLD_CHUNK; }
+
+// ---- IBN-a: InstanceNorm on channels [0, half), BatchNorm on [half, C) of ONE [N][C][HW] tensor -------------------------------
+// The reference writes the layer as split -> contiguous x 2 -> two norms -> cat (CC/clustercontrast/models/resnet_ibn_a.py:54-68):
+// six extra passes over the activation per direction.  Here both halves are normalised in place of layout: the only tensors of
+// the activation's size are x, y (forward) and x, dy, y, dx (backward).
+//   row kernels     one lane group (16 / 32 / 64 lanes, or the workgroup) per row (n, c) of HW contiguous floats, as the
+//                   InstanceNorm kernels above, the row in registers when it fits (at most 8 float4 per lane), loops otherwise.  An IN row forms its own statistics / sums (two-pass, biased variance); a BN row
+//                   takes the channel's statistics (running ones in eval mode, the batch ones of the slice-parallel
+//                   bn_stats_partial / bn_bwd_reduce_partial kernels, run over the channel sub-range with the full tensor's
+//                   sample stride, in train mode).  A lane group is one kind of row, so the branches are group-uniform.
+//   fused kernels   train mode with N*HW <= 16384: workgroups [0, C - half) each own one BN channel (bn_channel_fwd / _bwd, the
+//                   one-workgroup-per-channel scheme), the rest of the grid are IN lane groups: one launch per direction.
+// Backward sums: IN rows write sum g and sum g*xhat per instance, eval-mode BN rows per (n, channel) as well (their dx needs no
+// channel sum, so the row is read once); rows_sum_pair_kernel adds them over n into the four affine gradients.  Train-mode BN
+// channel sums come from the channel workgroups / the slice reduction and ARE dbeta / dgamma.  Fixed summation order, no atomics.
+template <int LANES>
+__device__ __forceinline__ void ibn_row_fwd(const float* __restrict__ xp, float* __restrict__ yp, int HW, int t, float* red,
+                                            bool own_stats, float mu, float is, float eps, float g, float b, int act,
+                                            float* __restrict__ mean_out, float* __restrict__ invstd_out) {
+    constexpr int T = LANES;
+    const bool vec = (HW & 3) == 0;
+    const int nv = HW >> 2;
+    if (own_stats) {                                              // uniform over the lane group (LANES == 256: the workgroup)
+        float s = 0.f;
+        if (vec) {
+            for (int i = t; i < nv; i += T) {
+                const float4 v = reinterpret_cast<const float4*>(xp)[i];
+                s += (v.x + v.y) + (v.z + v.w);
+            }
+        } else {
+            for (int i = t; i < HW; i += T) s += xp[i];
+        }
+        mu = in_reduce<LANES>(s, red) / (float)HW;
+        float q = 0.f;
+        if (vec) {
+            for (int i = t; i < nv; i += T) {
+                const float4 v = reinterpret_cast<const float4*>(xp)[i];
+                const float a = v.x - mu, bb = v.y - mu, c = v.z - mu, d = v.w - mu;
+                q += (a * a + bb * bb) + (c * c + d * d);
+            }
+        } else {
+            for (int i = t; i < HW; i += T) {
+                const float a = xp[i] - mu;
+                q += a * a;
+            }
+        }
+        is = rsqrtf(in_reduce<LANES>(q, red) / (float)HW + eps);
+        if (t == 0) {
+            *mean_out = mu;
+            *invstd_out = is;
+        }
+    }
+    const float gs = g * is;
+    const float sh = b - mu * gs;
+    if (vec) {
+        for (int i = t; i < nv; i += T) {
+            const float4 v = reinterpret_cast<const float4*>(xp)[i];
+            float4 o;
+            o.x = rg_apply_act(v.x * gs + sh, act, 0.f); o.y = rg_apply_act(v.y * gs + sh, act, 0.f);
+            o.z = rg_apply_act(v.z * gs + sh, act, 0.f); o.w = rg_apply_act(v.w * gs + sh, act, 0.f);
+            reinterpret_cast<float4*>(yp)[i] = o;
+        }
+    } else {
+        for (int i = t; i < HW; i += T) yp[i] = rg_apply_act(xp[i] * gs + sh, act, 0.f);
+    }
+}
+
+enum { IBN_ROW_IN = 0, IBN_ROW_BN_TRAIN = 1, IBN_ROW_BN_EVAL = 2 };
+
+// g = dy * act'(y); dx = gs * (g - a - (x - mu) * b).  IN row: a, b from its own sums (first pass); BN train row: a, b given (channel
+// sums); BN eval row: a = b = 0 and the sums are gathered in the same pass.  s1 / s2 are written except for BN train rows.
+template <int LANES>
+__device__ __forceinline__ void ibn_row_bwd(const float* __restrict__ xp, const float* __restrict__ gp, const float* __restrict__ yp,
+                                            float* __restrict__ dxp, int HW, int t, float* red, int kind, float mu, float is,
+                                            float gs, float a, float b, int act, float* __restrict__ s1_out,
+                                            float* __restrict__ s2_out) {
+    constexpr int T = LANES;
+    const bool vec = (HW & 3) == 0;
+    const int nv = HW >> 2;
+    float s1 = 0.f, s2 = 0.f;
+    if (kind == IBN_ROW_IN) {
+        if (vec) {
+            for (int i = t; i < nv; i += T) {
+                float4 g = reinterpret_cast<const float4*>(gp)[i];
+                if (yp) {
+                    const float4 yv = reinterpret_cast<const float4*>(yp)[i];
+                    g.x *= act_grad_from_out(yv.x, act, 0.f); g.y *= act_grad_from_out(yv.y, act, 0.f);
+                    g.z *= act_grad_from_out(yv.z, act, 0.f); g.w *= act_grad_from_out(yv.w, act, 0.f);
+                }
+                const float4 v = reinterpret_cast<const float4*>(xp)[i];
+                s1 += (g.x + g.y) + (g.z + g.w);
+                s2 += (g.x * (v.x - mu) + g.y * (v.y - mu)) + (g.z * (v.z - mu) + g.w * (v.w - mu));
+            }
+        } else {
+            for (int i = t; i < HW; i += T) {
+                float g = gp[i];
+                if (yp) g *= act_grad_from_out(yp[i], act, 0.f);
+                s1 += g;
+                s2 += g * (xp[i] - mu);
+            }
+        }
+        s1 = in_reduce<LANES>(s1, red);
+        s2 = in_reduce<LANES>(s2, red) * is;
+        if (t == 0) {
+            *s1_out = s1;
+            *s2_out = s2;
+        }
+        a = s1 / (float)HW;
+        b = s2 / (float)HW * is;
+        s1 = s2 = 0.f;
+    }
+    if (vec) {
+        for (int i = t; i < nv; i += T) {
+            float4 g = reinterpret_cast<const float4*>(gp)[i];
+            if (yp) {
+                const float4 yv = reinterpret_cast<const float4*>(yp)[i];
+                g.x *= act_grad_from_out(yv.x, act, 0.f); g.y *= act_grad_from_out(yv.y, act, 0.f);
+                g.z *= act_grad_from_out(yv.z, act, 0.f); g.w *= act_grad_from_out(yv.w, act, 0.f);
+            }
+            const float4 v = reinterpret_cast<const float4*>(xp)[i];
+            const float d0 = v.x - mu, d1 = v.y - mu, d2 = v.z - mu, d3 = v.w - mu;
+            float4 o;
+            o.x = gs * (g.x - a - d0 * b); o.y = gs * (g.y - a - d1 * b);
+            o.z = gs * (g.z - a - d2 * b); o.w = gs * (g.w - a - d3 * b);
+            reinterpret_cast<float4*>(dxp)[i] = o;
+            s1 += (g.x + g.y) + (g.z + g.w);
+            s2 += (g.x * d0 + g.y * d1) + (g.z * d2 + g.w * d3);
+        }
+    } else {
+        for (int i = t; i < HW; i += T) {
+            float g = gp[i];
+            if (yp) g *= act_grad_from_out(yp[i], act, 0.f);
+            const float d = xp[i] - mu;
+            dxp[i] = gs * (g - a - d * b);
+            s1 += g;
+            s2 += g * d;
+        }
+    }
+    if (kind == IBN_ROW_BN_EVAL) {
+        s1 = in_reduce<LANES>(s1, red);
+        s2 = in_reduce<LANES>(s2, red) * is;
+        if (t == 0) {
+            *s1_out = s1;
+            *s2_out = s2;
+        }
+    }
+}
+
+// The same two rows with the row in registers (HW % 4 == 0, at most U float4 per lane: every IBN map of the ResNets up to 64 x 32):
+// each operand is loaded once, all loads of a lane in flight together, instead of one load per loop iteration and pass — what
+// instnorm_*_reg_kernel do for the plain InstanceNorm.  Same per-lane order and reductions as the loops above.
+template <int LANES, int U>
+__device__ __forceinline__ void ibn_row_fwd_reg(const float* __restrict__ xp, float* __restrict__ yp, int HW, int t, float* red,
+                                                bool own_stats, float mu, float is, float eps, float g, float b, int act,
+                                                float* __restrict__ mean_out, float* __restrict__ invstd_out) {
+    const int nv = HW >> 2;
+    float4 a[U];
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+        const int i = t + LANES * j;
+        a[j] = i < nv ? reinterpret_cast<const float4*>(xp)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    if (own_stats) {
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < U; ++j) s += (a[j].x + a[j].y) + (a[j].z + a[j].w);
+        mu = in_reduce<LANES>(s, red) / (float)HW;
+        float q = 0.f;
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            const float d0 = a[j].x - mu, d1 = a[j].y - mu, d2 = a[j].z - mu, d3 = a[j].w - mu;
+            q += t + LANES * j < nv ? (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3) : 0.f;
+        }
+        is = rsqrtf(in_reduce<LANES>(q, red) / (float)HW + eps);
+        if (t == 0) {
+            *mean_out = mu;
+            *invstd_out = is;
+        }
+    }
+    const float gs = g * is;
+    const float sh = b - mu * gs;
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+        const int i = t + LANES * j;
+        float4 o;
+        o.x = rg_apply_act(a[j].x * gs + sh, act, 0.f); o.y = rg_apply_act(a[j].y * gs + sh, act, 0.f);
+        o.z = rg_apply_act(a[j].z * gs + sh, act, 0.f); o.w = rg_apply_act(a[j].w * gs + sh, act, 0.f);
+        if (i < nv) reinterpret_cast<float4*>(yp)[i] = o;
+    }
+}
+
+template <int LANES, int U>
+__device__ __forceinline__ void ibn_row_bwd_reg(const float* __restrict__ xp, const float* __restrict__ gp, const float* __restrict__ yp,
+                                                float* __restrict__ dxp, int HW, int t, float* red, int kind, float mu, float is,
+                                                float gs, float a, float b, int act, float* __restrict__ s1_out,
+                                                float* __restrict__ s2_out) {
+    const int nv = HW >> 2;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 g[U], v[U];
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+        const int i = t + LANES * j;
+        g[j] = i < nv ? reinterpret_cast<const float4*>(gp)[i] : zero;
+        v[j] = i < nv ? reinterpret_cast<const float4*>(xp)[i] : make_float4(mu, mu, mu, mu);
+        if (yp) {
+            const float4 yv = i < nv ? reinterpret_cast<const float4*>(yp)[i] : zero;
+            g[j].x *= act_grad_from_out(yv.x, act, 0.f); g[j].y *= act_grad_from_out(yv.y, act, 0.f);
+            g[j].z *= act_grad_from_out(yv.z, act, 0.f); g[j].w *= act_grad_from_out(yv.w, act, 0.f);
+        }
+        v[j].x -= mu; v[j].y -= mu; v[j].z -= mu; v[j].w -= mu;
+    }
+    if (kind != IBN_ROW_BN_TRAIN) {                              // lanes past the row hold g = 0, x - mu = 0
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            s1 += (g[j].x + g[j].y) + (g[j].z + g[j].w);
+            s2 += (g[j].x * v[j].x + g[j].y * v[j].y) + (g[j].z * v[j].z + g[j].w * v[j].w);
+        }
+        s1 = in_reduce<LANES>(s1, red);
+        s2 = in_reduce<LANES>(s2, red) * is;
+        if (t == 0) {
+            *s1_out = s1;
+            *s2_out = s2;
+        }
+        if (kind == IBN_ROW_IN) {
+            a = s1 / (float)HW;
+            b = s2 / (float)HW * is;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+        const int i = t + LANES * j;
+        float4 o;
+        o.x = gs * (g[j].x - a - v[j].x * b); o.y = gs * (g[j].y - a - v[j].y * b);
+        o.z = gs * (g[j].z - a - v[j].z * b); o.w = gs * (g[j].w - a - v[j].w * b);
+        if (i < nv) reinterpret_cast<float4*>(dxp)[i] = o;
+    }
+}
+
+// U = 0: the loop rows; U > 0: the register rows
+template <int LANES, int U>
+__device__ __forceinline__ void ibn_fwd_row(const float* __restrict__ xp, float* __restrict__ yp, int HW, int t, float* red,
+                                            bool own_stats, float mu, float is, float eps, float g, float b, int act,
+                                            float* __restrict__ mean_out, float* __restrict__ invstd_out) {
+    if constexpr (U > 0) ibn_row_fwd_reg<LANES, U>(xp, yp, HW, t, red, own_stats, mu, is, eps, g, b, act, mean_out, invstd_out);
+    else ibn_row_fwd<LANES>(xp, yp, HW, t, red, own_stats, mu, is, eps, g, b, act, mean_out, invstd_out);
+}
+
+template <int LANES, int U>
+__device__ __forceinline__ void ibn_bwd_row(const float* __restrict__ xp, const float* __restrict__ gp, const float* __restrict__ yp,
+                                            float* __restrict__ dxp, int HW, int t, float* red, int kind, float mu, float is, float gs,
+                                            float a, float b, int act, float* __restrict__ s1_out, float* __restrict__ s2_out) {
+    if constexpr (U > 0) ibn_row_bwd_reg<LANES, U>(xp, gp, yp, dxp, HW, t, red, kind, mu, is, gs, a, b, act, s1_out, s2_out);
+    else ibn_row_bwd<LANES>(xp, gp, yp, dxp, HW, t, red, kind, mu, is, gs, a, b, act, s1_out, s2_out);
+}
+
+// every row (n, c) of the tensor; BN rows use bn_mean / bn_stat [C - half] (stat_is_var: a variance, eps applied here)
+template <int LANES, int U>
+__global__ __launch_bounds__(256) void ibn_fwd_rows_kernel(const float* __restrict__ x, const float* __restrict__ in_gamma,
+                                                           const float* __restrict__ in_beta, const float* __restrict__ bn_gamma,
+                                                           const float* __restrict__ bn_beta, const float* __restrict__ bn_mean,
+                                                           const float* __restrict__ bn_stat, float* __restrict__ y,
+                                                           float* __restrict__ in_mean, float* __restrict__ in_invstd, int NC, int C,
+                                                           int half, int HW, int stat_is_var, float in_eps, float bn_eps, int act) {
+    __shared__ float red[4];
+    const int row = (int)blockIdx.x * (256 / LANES) + (int)threadIdx.x / LANES;
+    if (row >= NC) return;                                       // whole lane groups leave (LANES == 256: grid = NC)
+    const int t = (int)threadIdx.x % LANES;
+    const int n = row / C, c = row - n * C;
+    const int64_t base = (int64_t)row * HW;
+    if (c < half) {
+        const int inst = n * half + c;
+        ibn_fwd_row<LANES, U>(x + base, y + base, HW, t, red, true, 0.f, 0.f, in_eps, in_gamma ? in_gamma[c] : 1.f,
+                              in_beta ? in_beta[c] : 0.f, act, in_mean + inst, in_invstd + inst);
+    } else {
+        const int sc = c - half;
+        float is = bn_stat[sc];
+        if (stat_is_var) is = rsqrtf(is + bn_eps);
+        ibn_fwd_row<LANES, U>(x + base, y + base, HW, t, red, false, bn_mean[sc], is, 0.f, bn_gamma ? bn_gamma[sc] : 1.f,
+                              bn_beta ? bn_beta[sc] : 0.f, act, nullptr, nullptr);
+    }
+}
+
+// grid = (C - half) BN channel workgroups, then the IN lane groups over the N * half instances
+template <int LANES, int U>
+__global__ __launch_bounds__(256) void ibn_train_fwd_fused_kernel(const float* __restrict__ x, const float* __restrict__ in_gamma,
+                                                                  const float* __restrict__ in_beta, const float* __restrict__ bn_gamma,
+                                                                  const float* __restrict__ bn_beta, float* __restrict__ y,
+                                                                  float* __restrict__ in_mean, float* __restrict__ in_invstd,
+                                                                  float* __restrict__ bn_mean, float* __restrict__ bn_invstd,
+                                                                  float* __restrict__ running_mean, float* __restrict__ running_var,
+                                                                  int N, int C, int half, int HW, float in_eps, float bn_eps,
+                                                                  float momentum, int act) {
+    __shared__ float red[4];
+    const int cb = C - half;
+    if ((int)blockIdx.x < cb) {                                   // workgroup-uniform
+        bn_channel_fwd(x, bn_gamma, bn_beta, nullptr, y, bn_mean, bn_invstd, running_mean, running_var, N, C, HW, bn_eps, momentum,
+                       act, 0.f, half + (int)blockIdx.x, (int)blockIdx.x, red);
+        return;
+    }
+    const int inst = ((int)blockIdx.x - cb) * (256 / LANES) + (int)threadIdx.x / LANES;
+    if (inst >= N * half) return;
+    const int t = (int)threadIdx.x % LANES;
+    const int n = inst / half, c = inst - n * half;
+    const int64_t base = ((int64_t)n * C + c) * HW;
+    ibn_fwd_row<LANES, U>(x + base, y + base, HW, t, red, true, 0.f, 0.f, in_eps, in_gamma ? in_gamma[c] : 1.f, in_beta ? in_beta[c] : 0.f,
+                          act, in_mean + inst, in_invstd + inst);
+}
+
+// every row of the tensor.  Row sums go to row_s1 / row_s2 [N][W]: W = half in train mode (IN rows only; the BN rows take the channel
+// sums bn_s1 / bn_s2 [C - half]), W = C in eval mode (BN rows write theirs too).
+template <int LANES, int U>
+__global__ __launch_bounds__(256) void ibn_bwd_rows_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+                                                           const float* __restrict__ yact, const float* __restrict__ in_mean,
+                                                           const float* __restrict__ in_invstd, const float* __restrict__ in_gamma,
+                                                           const float* __restrict__ bn_mean, const float* __restrict__ bn_stat,
+                                                           const float* __restrict__ bn_gamma, const float* __restrict__ bn_s1,
+                                                           const float* __restrict__ bn_s2, float* __restrict__ dx,
+                                                           float* __restrict__ row_s1, float* __restrict__ row_s2, int NC, int C,
+                                                           int half, int HW, int train, float bn_eps, float inv_count, int act) {
+    __shared__ float red[4];
+    const int row = (int)blockIdx.x * (256 / LANES) + (int)threadIdx.x / LANES;
+    if (row >= NC) return;
+    const int t = (int)threadIdx.x % LANES;
+    const int n = row / C, c = row - n * C;
+    const int64_t base = (int64_t)row * HW;
+    const float* yp = act != RG_ACT_NONE ? yact + base : nullptr;
+    const int W = train ? half : C;
+    if (c < half) {
+        const int inst = n * half + c;
+        const float is = in_invstd[inst];
+        ibn_bwd_row<LANES, U>(x + base, dy + base, yp, dx + base, HW, t, red, IBN_ROW_IN, in_mean[inst], is,
+                              (in_gamma ? in_gamma[c] : 1.f) * is, 0.f, 0.f, act, row_s1 + n * W + c, row_s2 + n * W + c);
+    } else if (train) {
+        const int sc = c - half;
+        const float is = bn_stat[sc];
+        ibn_bwd_row<LANES, U>(x + base, dy + base, yp, dx + base, HW, t, red, IBN_ROW_BN_TRAIN, bn_mean[sc], is,
+                              (bn_gamma ? bn_gamma[sc] : 1.f) * is, bn_s1[sc] * inv_count, bn_s2[sc] * inv_count * is, act, nullptr,
+                              nullptr);
+    } else {
+        const int sc = c - half;
+        const float is = rsqrtf(bn_stat[sc] + bn_eps);
+        ibn_bwd_row<LANES, U>(x + base, dy + base, yp, dx + base, HW, t, red, IBN_ROW_BN_EVAL, bn_mean[sc], is,
+                              (bn_gamma ? bn_gamma[sc] : 1.f) * is, 0.f, 0.f, act, row_s1 + n * W + c, row_s2 + n * W + c);
+    }
+}
+
+template <int LANES, int U>
+__global__ __launch_bounds__(256) void ibn_train_bwd_fused_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+                                                                  const float* __restrict__ yact, const float* __restrict__ in_mean,
+                                                                  const float* __restrict__ in_invstd, const float* __restrict__ in_gamma,
+                                                                  const float* __restrict__ bn_mean, const float* __restrict__ bn_invstd,
+                                                                  const float* __restrict__ bn_gamma, float* __restrict__ dx,
+                                                                  float* __restrict__ row_s1, float* __restrict__ row_s2,
+                                                                  float* __restrict__ bn_s1, float* __restrict__ bn_s2, int N, int C,
+                                                                  int half, int HW, int act) {
+    __shared__ float red[4];
+    const int cb = C - half;
+    if ((int)blockIdx.x < cb) {
+        bn_channel_bwd(x, dy, yact, bn_mean, bn_invstd, bn_gamma, dx, nullptr, bn_s1, bn_s2, N, C, HW, act, 0.f,
+                       half + (int)blockIdx.x, (int)blockIdx.x, red);
+        return;
+    }
+    const int inst = ((int)blockIdx.x - cb) * (256 / LANES) + (int)threadIdx.x / LANES;
+    if (inst >= N * half) return;
+    const int t = (int)threadIdx.x % LANES;
+    const int n = inst / half, c = inst - n * half;
+    const int64_t base = ((int64_t)n * C + c) * HW;
+    const float is = in_invstd[inst];
+    ibn_bwd_row<LANES, U>(x + base, dy + base, act != RG_ACT_NONE ? yact + base : nullptr, dx + base, HW, t, red, IBN_ROW_IN,
+                          in_mean[inst], is, (in_gamma ? in_gamma[c] : 1.f) * is, 0.f, 0.f, act, row_s1 + inst, row_s2 + inst);
+}
+
+static bool ibn_train_fused(int N, int HW) { return (int64_t)N * HW <= 16384; }
+
+// float4 per lane of the register rows for this map (2 or 8), 0 = the loop rows
+static int ibn_reg_units(int HW) {
+    if (!g_bn_reg || (HW & 3)) return 0;
+    const int lanes = in_lanes(HW);
+    const int per = ((HW >> 2) + lanes - 1) / lanes;
+    return per <= 2 ? 2 : per <= 8 ? 8 : 0;
+}
+
+// lane-group dispatch of the four kernels above: ROWS lane groups after LEAD whole workgroups
+#define RG_IBN_CASE(KERNEL, L_, U_, LEAD, ROWS, ...)                                                                                    \
+    case L_ * 16 + U_:                                                                                                                 \
+        hipLaunchKernelGGL((KERNEL<L_, U_>), dim3((LEAD) + rg::cdiv(ROWS, 256 / L_)), dim3(256), 0, stream, __VA_ARGS__);                \
+        break
+#define RG_IBN_LAUNCH(KERNEL, LEAD, ROWS, ...)                                                                                          \
+    switch (in_lanes(HW) * 16 + ibn_reg_units(HW)) {                                                                                   \
+        RG_IBN_CASE(KERNEL, 16, 0, LEAD, ROWS, __VA_ARGS__); RG_IBN_CASE(KERNEL, 16, 2, LEAD, ROWS, __VA_ARGS__);                        \
+        RG_IBN_CASE(KERNEL, 32, 0, LEAD, ROWS, __VA_ARGS__); RG_IBN_CASE(KERNEL, 32, 2, LEAD, ROWS, __VA_ARGS__);                        \
+        RG_IBN_CASE(KERNEL, 64, 0, LEAD, ROWS, __VA_ARGS__); RG_IBN_CASE(KERNEL, 64, 2, LEAD, ROWS, __VA_ARGS__);                        \
+        RG_IBN_CASE(KERNEL, 64, 8, LEAD, ROWS, __VA_ARGS__);                                                                           \
+        RG_IBN_CASE(KERNEL, 256, 0, LEAD, ROWS, __VA_ARGS__); RG_IBN_CASE(KERNEL, 256, 8, LEAD, ROWS, __VA_ARGS__);                      \
+        default: rg::set_error("rg_ibn: no kernel for %d lanes x %d units", in_lanes(HW), ibn_reg_units(HW)); return RG_ERR_INVALID;    \
+    }
+
+// bytes of workspace for rg_ibn_fwd / rg_ibn_bwd: the slice partials of the BN half, then the row sums [2][N][C]
+extern "C" int64_t rg_ibn_workspace(int N, int C, int HW, int half) {
+    if (N <= 0 || C <= 0 || HW <= 0 || half <= 0 || half >= C) return 0;
+    int L;
+    const int S = pick_slices(N, C - half, HW, &L);
+    return (int64_t)(((size_t)(C - half) * S * 3 + (size_t)2 * N * C) * sizeof(float));
+}
+
+extern "C" int rg_ibn_fwd(const float* x, const float* in_gamma, const float* in_beta, const float* bn_gamma, const float* bn_beta,
+                          const float* residual, float* y, float* in_mean, float* in_invstd, float* bn_mean, float* bn_invstd,
+                          float* running_mean, float* running_var, int N, int C, int HW, int half, int train, float in_eps,
+                          float bn_eps, float momentum, int act, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    RG_REQUIRE(x && y && in_mean && in_invstd && N > 0 && C > 0 && HW > 0, "rg_ibn_fwd: bad arguments");
+    RG_REQUIRE(half > 0 && half < C, "rg_ibn_fwd: the split point %d must lie inside the %d channels", half, C);
+    RG_REQUIRE(!residual, "rg_ibn_fwd: the layer has no residual input (bn1 of a Bottleneck never has one)");
+    RG_REQUIRE(act == RG_ACT_NONE || act == RG_ACT_RELU, "rg_ibn_fwd: activation %d (none or ReLU)", act);
+    RG_REQUIRE((int64_t)N * C < (1ll << 31) && (int64_t)N * HW < (1ll << 30), "rg_ibn_fwd: N*C or N*HW too large");
+    RG_REQUIRE(train ? (bn_mean && bn_invstd) : (running_mean && running_var),
+               train ? "rg_ibn_fwd: train mode writes the batch statistics" : "rg_ibn_fwd: eval mode needs the running statistics");
+    const int NC = N * C, cb = C - half;
+    rg::ProfScope prof(rg::FAM_NORM, stream, 0.0, 8.0 * (double)NC * HW);
+    if (!train) {
+        RG_IBN_LAUNCH(ibn_fwd_rows_kernel, 0, NC, x, in_gamma, in_beta, bn_gamma, bn_beta, running_mean, running_var, y, in_mean,
+                      in_invstd, NC, C, half, HW, 1, in_eps, bn_eps, act);
+        return rg::check_launch("rg_ibn_fwd");
+    }
+    if (ibn_train_fused(N, HW)) {
+        RG_IBN_LAUNCH(ibn_train_fwd_fused_kernel, cb, N * half, x, in_gamma, in_beta, bn_gamma, bn_beta, y, in_mean, in_invstd, bn_mean,
+                      bn_invstd, running_mean, running_var, N, C, half, HW, in_eps, bn_eps, momentum, act);
+        return rg::check_launch("rg_ibn_fwd");
+    }
+    int L;
+    const int S = pick_slices(N, cb, HW, &L);
+    if (!workspace || workspace_bytes < (size_t)cb * S * 3 * sizeof(float)) {
+        rg::set_error("rg_ibn_fwd: workspace too small");
+        return RG_ERR_WORKSPACE;
+    }
+    float* part = static_cast<float*>(workspace);
+    // the BN half's statistics: the slice kernels over channels [half, C) — same sample stride C*HW, channel 0 of the view = half
+    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(S, cb), dim3(256), 0, stream, x + (int64_t)half * HW, part, N, C, HW, L);
+    hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(rg::cdiv(cb, 64)), dim3(64), 0, stream, part, cb, S, bn_eps, momentum, bn_mean,
+                       bn_invstd, running_mean, running_var);
+    RG_IBN_LAUNCH(ibn_fwd_rows_kernel, 0, NC, x, in_gamma, in_beta, bn_gamma, bn_beta, bn_mean, bn_invstd, y, in_mean, in_invstd, NC, C,
+                  half, HW, 0, in_eps, bn_eps, act);
+    return rg::check_launch("rg_ibn_fwd");
+}
+
+// dx and the four affine gradients.  bn_mean / bn_stat: the saved batch mean / invstd (train) or the running mean / variance (eval).
+extern "C" int rg_ibn_bwd(const float* x, const float* dy, const float* y_act, const float* in_mean, const float* in_invstd,
+                          const float* bn_mean, const float* bn_stat, const float* in_gamma, const float* bn_gamma, float* dx,
+                          float* d_in_gamma, float* d_in_beta, float* d_bn_gamma, float* d_bn_beta, int N, int C, int HW, int half,
+                          int train, float bn_eps, int act, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    RG_REQUIRE(x && dy && in_mean && in_invstd && bn_mean && bn_stat && dx && N > 0 && C > 0 && HW > 0, "rg_ibn_bwd: bad arguments");
+    RG_REQUIRE(d_in_gamma && d_in_beta && d_bn_gamma && d_bn_beta, "rg_ibn_bwd: the four affine gradients are outputs");
+    RG_REQUIRE(half > 0 && half < C, "rg_ibn_bwd: the split point %d must lie inside the %d channels", half, C);
+    RG_REQUIRE(act == RG_ACT_NONE || act == RG_ACT_RELU, "rg_ibn_bwd: activation %d (none or ReLU)", act);
+    RG_REQUIRE(act == RG_ACT_NONE || y_act, "rg_ibn_bwd: fused activation needs the forward output");
+    RG_REQUIRE((int64_t)N * C < (1ll << 31) && (int64_t)N * HW < (1ll << 30), "rg_ibn_bwd: N*C or N*HW too large");
+    const int NC = N * C, cb = C - half;
+    int L;
+    const int S = pick_slices(N, cb, HW, &L);
+    const size_t part_floats = (size_t)cb * S * 3;
+    if (!workspace || workspace_bytes < (part_floats + (size_t)2 * NC) * sizeof(float)) {
+        rg::set_error("rg_ibn_bwd: workspace too small");
+        return RG_ERR_WORKSPACE;
+    }
+    float* part = static_cast<float*>(workspace);
+    float* row_s1 = part + part_floats;
+    float* row_s2 = row_s1 + NC;
+    rg::ProfScope prof(rg::FAM_NORM, stream, 0.0, (act ? 16.0 : 12.0) * (double)NC * HW);
+    if (!train) {
+        RG_IBN_LAUNCH(ibn_bwd_rows_kernel, 0, NC, x, dy, y_act, in_mean, in_invstd, in_gamma, bn_mean, bn_stat, bn_gamma, nullptr,
+                      nullptr, dx, row_s1, row_s2, NC, C, half, HW, 0, bn_eps, 0.f, act);
+        hipLaunchKernelGGL(rows_sum_pair_kernel, dim3(rg::cdiv(C, 16)), dim3(256), 0, stream, row_s1, row_s2, d_in_beta, d_in_gamma, N,
+                           C, half, d_bn_beta, d_bn_gamma);
+        return rg::check_launch("rg_ibn_bwd");
+    }
+    if (ibn_train_fused(N, HW)) {
+        RG_IBN_LAUNCH(ibn_train_bwd_fused_kernel, cb, N * half, x, dy, y_act, in_mean, in_invstd, in_gamma, bn_mean, bn_stat, bn_gamma,
+                      dx, row_s1, row_s2, d_bn_beta, d_bn_gamma, N, C, half, HW, act);
+    } else {
+        const int64_t off = (int64_t)half * HW;
+        hipLaunchKernelGGL(bn_bwd_reduce_partial_kernel, dim3(S, cb), dim3(256), 0, stream, x + off, dy + off,
+                           y_act ? y_act + off : nullptr, bn_mean, bn_stat, part, N, C, HW, L, 0, bn_eps, act, 0.f);
+        hipLaunchKernelGGL(bn_bwd_reduce_finalize_kernel, dim3(rg::cdiv(cb, 64)), dim3(64), 0, stream, part, cb, S, d_bn_beta,
+                           d_bn_gamma);
+        RG_IBN_LAUNCH(ibn_bwd_rows_kernel, 0, NC, x, dy, y_act, in_mean, in_invstd, in_gamma, bn_mean, bn_stat, bn_gamma, d_bn_beta,
+                      d_bn_gamma, dx, row_s1, row_s2, NC, C, half, HW, 1, bn_eps, 1.f / (float)((int64_t)N * HW), act);
+    }
+    hipLaunchKernelGGL(rows_sum_pair_kernel, dim3(rg::cdiv(half, 16)), dim3(256), 0, stream, row_s1, row_s2, d_in_beta, d_in_gamma, N,
+                       half, half, nullptr, nullptr);
+    return rg::check_launch("rg_ibn_bwd");
+}
+#undef RG_IBN_LAUNCH
+#undef RG_IBN_CASE

@@ -857,6 +857,47 @@ class InstanceNorm1d(InstanceNorm2d):
         return out.squeeze(-1)
 
 
+class IBN(RGModule):
+    """The IBN layer of the IBN-a ResNets (CC/clustercontrast/models/resnet_ibn_a.py:54-68): InstanceNorm2d(half, affine) on the
+    first `half` channels, BatchNorm2d on the rest.  The children `IN` / `BN` only hold the parameters and running statistics
+    (so the reference's state_dict keys load unchanged); the arithmetic is `rg_ibn_fwd` / `rg_ibn_bwd` on the whole tensor —
+    no slice copies, no concatenation."""
+
+    def __init__(self, planes):
+        super(IBN, self).__init__()
+        half1 = int(planes / 2)
+        self.half = half1
+        self.IN = InstanceNorm2d(half1, affine=True)
+        self.BN = BatchNorm2d(planes - half1)
+
+    def tf(self, tape, x, residual=None, act=ACT_NONE, slope=0.0):
+        bn = self.BN
+        train = bn.training
+        if train:
+            bn.__dict__["_nbt_pending"] = bn.__dict__.get("_nbt_pending", 0) + 1          # as _BatchNorm.tf
+        y, in_mean, in_invstd, bn_mean, bn_invstd = ops.ibn_fwd(
+            x, self.half, self.IN.weight.detach(), self.IN.bias.detach(), bn.weight.detach(), bn.bias.detach(), bn.running_mean,
+            bn.running_var, train, self.IN.eps, bn.eps, bn.momentum, residual=residual, act=act)
+        if not train:
+            bn_mean, bn_invstd = bn.running_mean, bn.running_var
+        tape.push((x, y if act != ACT_NONE else None, in_mean, in_invstd, bn_mean, bn_invstd, train, act))
+        return y
+
+    def tb(self, tape, dy, need_dx=True, dy_masked=False):
+        """dy_masked: the consumer's dgrad already applied this layer's ReLU mask (see _BatchNorm.tb): y is not read."""
+        x, y, in_mean, in_invstd, bn_mean, bn_stat, train, act = tape.pop()
+        if dy_masked:
+            act, y = ACT_NONE, None
+        params = (self.IN.weight, self.IN.bias, self.BN.weight, self.BN.bias)
+        out = tuple(tape.grad_out(p) if tape.wants(p) else None for p in params)
+        res = ops.ibn_bwd(x, dy, y, self.half, in_mean, in_invstd, bn_mean, bn_stat, self.IN.weight.detach(),
+                          self.BN.weight.detach(), train, self.BN.eps, act, out=out)
+        for p, g in zip(params, res[1:]):
+            if tape.wants(p):
+                tape.add_grad(p, g)
+        return res[0]
+
+
 class AvgPool2d(RGModule):
     """nn.AvgPool2d(kernel_size=k, stride=k) (the only form the dual_gan blocks use)."""
 

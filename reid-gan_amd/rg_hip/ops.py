@@ -567,6 +567,41 @@ def rows_sum_pair(a, b, N, C, out_a=None, out_b=None):
     return out_a, out_b
 
 
+def ibn_fwd(x, half, in_gamma, in_beta, bn_gamma, bn_beta, running_mean, running_var, train, in_eps=1e-5, bn_eps=1e-5,
+            momentum=0.1, residual=None, act=ACT_NONE):
+    """IBN layer (InstanceNorm on channels [0, half), BatchNorm on the rest) on the whole tensor, no slice / cat copies
+    -> (y, in_mean[N*half], in_invstd[N*half], bn_mean[C-half], bn_invstd[C-half]); the BN statistics are None in eval mode."""
+    x, residual = _chk(x, "x"), _chk(residual, "residual")
+    _same_size("ibn_fwd", x, residual=residual)
+    N, C, HW = _nchw(x)
+    y = torch.empty_like(x)
+    in_stats = torch.empty(2, N * half, dtype=torch.float32, device=x.device)
+    bn_stats_ = torch.empty(2, C - half, dtype=torch.float32, device=x.device) if train else None
+    ws = workspace(_ws_query("rg_ibn_workspace", N, C, HW, half), x.device)
+    lib.rg_ibn_fwd(_p(x), _p(in_gamma), _p(in_beta), _p(bn_gamma), _p(bn_beta), _p(residual), _p(y), _p(in_stats[0]),
+                   _p(in_stats[1]), _p(bn_stats_[0]) if train else None, _p(bn_stats_[1]) if train else None,
+                   _p(running_mean), _p(running_var), N, C, HW, half, int(train), in_eps, bn_eps, momentum, act, _p(ws),
+                   ws.numel(), _stream())
+    return y, in_stats[0], in_stats[1], (bn_stats_[0] if train else None), (bn_stats_[1] if train else None)
+
+
+def ibn_bwd(x, dy, y_act, half, in_mean, in_invstd, bn_mean, bn_stat, in_gamma, bn_gamma, train, bn_eps=1e-5, act=ACT_NONE,
+            out=(None, None, None, None)):
+    """-> (dx, d_in_gamma, d_in_beta, d_bn_gamma, d_bn_beta).  bn_mean / bn_stat: the saved batch mean / invstd (train) or the
+    running mean / variance (eval).  `out`: preallocated gradient outputs in that order."""
+    x, dy, y_act = _chk(x, "x"), _chk(dy, "dy"), _chk(y_act, "y")
+    _same_size("ibn_bwd", dy, x=x, y=y_act)
+    N, C, HW = _nchw(x)
+    dx = torch.empty_like(dy)
+    sizes = (half, half, C - half, C - half)
+    grads = [o if o is not None else torch.empty(n, dtype=torch.float32, device=x.device) for o, n in zip(out, sizes)]
+    ws = workspace(_ws_query("rg_ibn_workspace", N, C, HW, half), x.device)
+    lib.rg_ibn_bwd(_p(x), _p(dy), _p(y_act), _p(in_mean), _p(in_invstd), _p(bn_mean), _p(bn_stat), _p(in_gamma), _p(bn_gamma),
+                   _p(dx), _p(grads[0]), _p(grads[1]), _p(grads[2]), _p(grads[3]), N, C, HW, half, int(train), bn_eps, act,
+                   _p(ws), ws.numel(), _stream())
+    return (dx,) + tuple(grads)
+
+
 def bn_bwd_apply(x, dy, y_act, mean, stat, gamma, sum_dy, sum_dy_xhat, train, stat_is_var=False, eps=1e-5,
                  act=ACT_NONE, slope=0.0, need_dx=True, need_dres=False):
     x, dy, y_act = _chk(x, "x"), _chk(dy, "dy"), _chk(y_act, "y")

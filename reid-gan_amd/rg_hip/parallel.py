@@ -229,6 +229,7 @@ def attach_stage_hooks(reducer, *modules):
     """Give every ResNet trunk under `modules` the stage hook of `reducer`: its gradient all-reduce is then launched stage by stage
     from inside the trunk's backward program (layer4 first) instead of after it.  Returns the number of trunks found.  Harmless on
     one rank (the hook returns at once while the reducer is inactive)."""
+    from .nn import Sequential
     from .resnet_trunk import TVResNet
     n = 0
     if os.environ.get("RG_STAGE_BUCKETS", "1") == "0":       # A/B switch: one reduction per arena after the backward pass (round 3)
@@ -239,8 +240,10 @@ def attach_stage_hooks(reducer, *modules):
             mods = None
             if isinstance(m, TVResNet):
                 mods = m.trunk_modules()
-            elif hasattr(m, "base") and isinstance(getattr(m, "base"), nn.Sequential) and len(m.base) >= 8:
-                mods = list(m.base)                   # clustercontrast ResNet: `base` is the trunk as a Sequential
+            elif hasattr(m, "base") and isinstance(getattr(m, "base"), (nn.Sequential, Sequential)) and len(m.base) >= 8:
+                # clustercontrast ResNet / ResNetIBN: `base` is the trunk as a Sequential (rg_hip.nn.Sequential is an RGModule,
+                # not a torch.nn.Sequential)
+                mods = list(m.base)
             if mods is not None and hasattr(mods[0], "weight"):
                 mods[0].__dict__["_rg_stage_hook"] = reducer.reduce_stage
                 n += 1

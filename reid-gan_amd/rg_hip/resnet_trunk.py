@@ -21,10 +21,10 @@ from .tape import RGModule
 class Bottleneck(RGModule):
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, ibn=False):
         super(Bottleneck, self).__init__()
         self.conv1 = rnn.Conv2d(inplanes, planes, 1, bias=False)
-        self.bn1 = rnn.BatchNorm2d(planes)
+        self.bn1 = rnn.IBN(planes) if ibn else rnn.BatchNorm2d(planes)     # IBN-a: CC/.../resnet_ibn_a.py:73-79
         self.conv2 = rnn.Conv2d(planes, planes, 3, stride=stride, padding=1, bias=False)
         self.bn2 = rnn.BatchNorm2d(planes)
         self.conv3 = rnn.Conv2d(planes, planes * 4, 1, bias=False)
@@ -89,6 +89,8 @@ _CFG = {
     50: (Bottleneck, [3, 4, 6, 3]),
     101: (Bottleneck, [3, 4, 23, 3]),
     152: (Bottleneck, [3, 8, 36, 3]),
+    "50a": (Bottleneck, [3, 4, 6, 3]),              # IBN-a depths (IBNResNet), CC/clustercontrast/models/resnet_ibn_a.py:179-202
+    "101a": (Bottleneck, [3, 4, 23, 3]),
 }
 
 
@@ -119,11 +121,15 @@ class TVResNet(RGModule):
             downsample = rnn.Sequential(
                 rnn.Conv2d(self.inplanes, planes * block.expansion, 1, stride=stride, bias=False),
                 rnn.BatchNorm2d(planes * block.expansion))
-        layers = [block(self.inplanes, planes, stride, downsample)]
+        kw = self._block_args(planes)
+        layers = [block(self.inplanes, planes, stride, downsample, **kw)]
         self.inplanes = planes * block.expansion
         for _ in range(1, blocks):
-            layers.append(block(self.inplanes, planes))
+            layers.append(block(self.inplanes, planes, **kw))
         return rnn.Sequential(*layers)
+
+    def _block_args(self, planes):
+        return {}
 
     def trunk_modules(self):
         return [self.conv1, self.bn1, self.relu, self.maxpool, self.layer1, self.layer2, self.layer3, self.layer4]
@@ -135,7 +141,21 @@ class TVResNet(RGModule):
         return trunk_tb(tape, self.trunk_modules(), dy, need_dx)
 
 
+class IBNResNet(TVResNet):
+    """IBN-a trunk ('50a' / '101a'): bn1 of every block of layer1..layer3 is an IBN layer, layer4 keeps BatchNorm
+    (CC/clustercontrast/models/resnet_ibn_a.py:141-159: `ibn = planes != 512` for every block of the layer)."""
+
+    def _block_args(self, planes):
+        return {"ibn": planes != 512}
+
+
 def _conv_bn_pairs(mods):
+    """the (conv, BatchNorm) pairs a FoldGroup folds; an IBN layer is not a per-channel affine map of the conv output (its IN half
+    depends on the sample), so its pair stays on the unfused conv -> IBN path"""
+    return [(conv, bn) for conv, bn in _conv_norm_pairs(mods) if isinstance(bn, rnn._BatchNorm)]
+
+
+def _conv_norm_pairs(mods):
     pairs = [(mods[0], mods[1])]
     for layer in mods[4:]:
         for blk in layer:
@@ -196,6 +216,22 @@ def bn_all_eval(module):
         if isinstance(m, rnn._BatchNorm) and (m.training or not m.track_running_stats):
             return False
     return True
+
+
+def load_pretrained_ibn(model, depth):
+    """IBN-a ImageNet initialisation as CC/clustercontrast/models/resnet_ibn_a.py:10-13,186-188,205-209: a checkpoint
+    {'state_dict': ...} whose keys may carry a `module.` prefix, from $RG_RESNET_IBN{50A,101A}_WEIGHTS or the reference's
+    relative path; loaded strictly."""
+    env = "RG_RESNET_IBN%s_WEIGHTS" % str(depth).upper()
+    rel = os.path.join(".", "examples", "pretrained", "resnet%s_ibn_a.pth.tar" % str(depth)[:-1])
+    for path in (os.environ.get(env), rel):
+        if path and os.path.exists(path):
+            sd = torch.load(path, map_location="cpu")["state_dict"]
+            model.load_state_dict({k.replace("module.", ""): v for k, v in sd.items()}, strict=True)
+            return model
+    raise RuntimeError(
+        "pretrained=True needs the IBN-a ImageNet checkpoint for resnet_ibn%s, which the reference reads from %s; "
+        "not found: point %s at a local copy or pass pretrained=False" % (depth, rel, env))
 
 
 def load_pretrained(model, depth):

@@ -36,6 +36,8 @@ FAMILY = {
     "bn_train_fwd_reg_kernel": "norm", "channel_sum_small_kernel": "norm", "bn_train_bwd_reg_kernel": "norm", "instnorm_fwd_reg_kernel": "norm", "instnorm_bwd_reg_kernel": "norm",
     "rows_sum_pair_kernel": "norm", "scale_rows_kernel": "norm", "sum_slices_kernel": "norm",
     "bn_stats_from_partials_kernel": "norm", "bn_bwd_from_partials_kernel": "norm",
+    "ibn_fwd_rows_kernel": "norm", "ibn_train_fwd_fused_kernel": "norm", "ibn_bwd_rows_kernel": "norm",
+    "ibn_train_bwd_fused_kernel": "norm",
     # optim.hip
     "adam_advance_kernel": "optim", "adam_dev_kernel": "optim", "adam_kernel": "optim", "sgd_kernel": "optim",
     "u64_add_kernel": "optim",
