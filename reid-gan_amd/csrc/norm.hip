@@ -11,6 +11,7 @@
 //
 // Tensor layout: [N][C][HW] contiguous (HW = 1 for BatchNorm1d on [N][C]).
 #include "rg_common.h"
+#include <type_traits>
 
 namespace {
 
@@ -619,183 +620,6 @@ extern "C" int rg_bn_bwd_reduce(const float* x, const float* dy, const float* y_
     return rg::check_launch("rg_bn_bwd_reduce");
 }
 
-// ---- InstanceNorm2d in one launch per direction -----------------------------------------------------------------------
-// An instance (n, c) is HW contiguous floats: <= 32 KB for every map of the dual_gan / FD-GAN networks, so the second and third
-// pass over it hit L1 / L2.  LANES = 16 / 32 / 64 lanes per instance (several instances per wave for the small maps, shuffles only),
-// 256: one workgroup per instance.  Statistics: mean, then the centred sum of squares (two-pass, biased variance).
-template <int LANES>
-__device__ __forceinline__ float in_reduce(float v, float* red) {
-    // LANES <= 64: butterfly inside the aligned lane group (several instances share a wave); 256: the whole workgroup
-#pragma unroll
-    for (int off = (LANES < 64 ? LANES : 64) / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if (LANES <= 64) return v;
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wid] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-template <int LANES>
-__global__ __launch_bounds__(256) void instnorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                           const float* __restrict__ beta, const float* __restrict__ res,
-                                                           float* __restrict__ y, float* __restrict__ mean_out,
-                                                           float* __restrict__ invstd_out, int NC, int C, int HW, float eps,
-                                                           int act, float slope) {
-    __shared__ float red[4];
-    const int inst = (int)blockIdx.x * (256 / LANES) + (int)threadIdx.x / LANES;
-    if (inst >= NC) return;                                   // whole lane groups leave (LANES == 256: never taken, grid = NC)
-    const int t = (int)threadIdx.x % LANES;
-    constexpr int T = LANES;
-    const int64_t base = (int64_t)inst * HW;
-    const float* xp = x + base;
-    const bool vec = (HW & 3) == 0;
-    const int nv = HW >> 2;
-    float s = 0.f;
-    if (vec) {
-        for (int i = t; i < nv; i += T) {
-            const float4 v = reinterpret_cast<const float4*>(xp)[i];
-            s += (v.x + v.y) + (v.z + v.w);
-        }
-    } else {
-        for (int i = t; i < HW; i += T) s += xp[i];
-    }
-    const float mu = in_reduce<LANES>(s, red) / (float)HW;
-    float q = 0.f;
-    if (vec) {
-        for (int i = t; i < nv; i += T) {
-            const float4 v = reinterpret_cast<const float4*>(xp)[i];
-            const float a = v.x - mu, b = v.y - mu, c = v.z - mu, d = v.w - mu;
-            q += (a * a + b * b) + (c * c + d * d);
-        }
-    } else {
-        for (int i = t; i < HW; i += T) {
-            const float a = xp[i] - mu;
-            q += a * a;
-        }
-    }
-    const float is = rsqrtf(in_reduce<LANES>(q, red) / (float)HW + eps);
-    if (t == 0) {
-        mean_out[inst] = mu;
-        invstd_out[inst] = is;
-    }
-    const int c = inst % C;
-    const float gs = (gamma ? gamma[c] : 1.f) * is;
-    const float sh = (beta ? beta[c] : 0.f) - mu * gs;
-    float* yp = y + base;
-    const float* rp = res ? res + base : nullptr;
-    if (vec) {
-        for (int i = t; i < nv; i += T) {
-            const float4 v = reinterpret_cast<const float4*>(xp)[i];
-            float4 o;
-            o.x = v.x * gs + sh; o.y = v.y * gs + sh; o.z = v.z * gs + sh; o.w = v.w * gs + sh;
-            if (rp) {
-                const float4 r = reinterpret_cast<const float4*>(rp)[i];
-                o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;
-            }
-            o.x = rg_apply_act(o.x, act, slope); o.y = rg_apply_act(o.y, act, slope);
-            o.z = rg_apply_act(o.z, act, slope); o.w = rg_apply_act(o.w, act, slope);
-            reinterpret_cast<float4*>(yp)[i] = o;
-        }
-    } else {
-        for (int i = t; i < HW; i += T) {
-            float o = xp[i] * gs + sh;
-            if (rp) o += rp[i];
-            yp[i] = rg_apply_act(o, act, slope);
-        }
-    }
-}
-
-// g = dy * act'(y); s1 = sum g, s2 = sum g * xhat (written per instance for the affine gradients);
-// dx = gamma * invstd * (g - s1 / HW - xhat * s2 / HW); dres = g
-template <int LANES>
-__global__ __launch_bounds__(256) void instnorm_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy,
-                                                           const float* __restrict__ yact, const float* __restrict__ mean,
-                                                           const float* __restrict__ invstd, const float* __restrict__ gamma,
-                                                           float* __restrict__ dx, float* __restrict__ dres,
-                                                           float* __restrict__ sum_dy, float* __restrict__ sum_dy_xhat,
-                                                           float* __restrict__ sum_dx, int NC, int C, int HW, int act,
-                                                           float slope) {
-    __shared__ float red[4];
-    const int inst = (int)blockIdx.x * (256 / LANES) + (int)threadIdx.x / LANES;
-    if (inst >= NC) return;
-    const int t = (int)threadIdx.x % LANES;
-    constexpr int T = LANES;
-    const int64_t base = (int64_t)inst * HW;
-    const float* xp = x + base;
-    const float* gp = dy + base;
-    const float* yp = act != RG_ACT_NONE ? yact + base : nullptr;
-    const float mu = mean[inst], is = invstd[inst];
-    const bool vec = (HW & 3) == 0;
-    const int nv = HW >> 2;
-    float s1 = 0.f, s2 = 0.f;
-    if (vec) {
-        for (int i = t; i < nv; i += T) {
-            float4 g = reinterpret_cast<const float4*>(gp)[i];
-            if (yp) {
-                const float4 yv = reinterpret_cast<const float4*>(yp)[i];
-                g.x *= act_grad_from_out(yv.x, act, slope); g.y *= act_grad_from_out(yv.y, act, slope);
-                g.z *= act_grad_from_out(yv.z, act, slope); g.w *= act_grad_from_out(yv.w, act, slope);
-            }
-            const float4 v = reinterpret_cast<const float4*>(xp)[i];
-            s1 += (g.x + g.y) + (g.z + g.w);
-            s2 += (g.x * (v.x - mu) + g.y * (v.y - mu)) + (g.z * (v.z - mu) + g.w * (v.w - mu));
-        }
-    } else {
-        for (int i = t; i < HW; i += T) {
-            float g = gp[i];
-            if (yp) g *= act_grad_from_out(yp[i], act, slope);
-            s1 += g;
-            s2 += g * (xp[i] - mu);
-        }
-    }
-    s1 = in_reduce<LANES>(s1, red);
-    s2 = in_reduce<LANES>(s2, red) * is;
-    if (t == 0) {
-        sum_dy[inst] = s1;
-        sum_dy_xhat[inst] = s2;
-    }
-    const float gs = (gamma ? gamma[inst % C] : 1.f) * is;
-    const float a = s1 / (float)HW, b = s2 / (float)HW * is;
-    float* dxp = dx ? dx + base : nullptr;
-    float* drp = dres ? dres + base : nullptr;
-    float sdx = 0.f;
-    if (vec) {
-        for (int i = t; i < nv; i += T) {
-            float4 g = reinterpret_cast<const float4*>(gp)[i];
-            if (yp) {
-                const float4 yv = reinterpret_cast<const float4*>(yp)[i];
-                g.x *= act_grad_from_out(yv.x, act, slope); g.y *= act_grad_from_out(yv.y, act, slope);
-                g.z *= act_grad_from_out(yv.z, act, slope); g.w *= act_grad_from_out(yv.w, act, slope);
-            }
-            if (drp) reinterpret_cast<float4*>(drp)[i] = g;
-            if (dxp) {
-                const float4 v = reinterpret_cast<const float4*>(xp)[i];
-                float4 o;
-                o.x = gs * (g.x - a - (v.x - mu) * b); o.y = gs * (g.y - a - (v.y - mu) * b);
-                o.z = gs * (g.z - a - (v.z - mu) * b); o.w = gs * (g.w - a - (v.w - mu) * b);
-                reinterpret_cast<float4*>(dxp)[i] = o;
-                sdx += (o.x + o.y) + (o.z + o.w);
-            }
-        }
-    } else {
-        for (int i = t; i < HW; i += T) {
-            float g = gp[i];
-            if (yp) g *= act_grad_from_out(yp[i], act, slope);
-            if (drp) drp[i] = g;
-            if (dxp) {
-                const float o = gs * (g - a - (xp[i] - mu) * b);
-                dxp[i] = o;
-                sdx += o;
-            }
-        }
-    }
-    if (sum_dx) {                                                // uniform: the bias gradient of the convolution in front
-        sdx = in_reduce<LANES>(sdx, red);
-        if (t == 0) sum_dx[inst] = sdx;
-    }
-}
-
 // ---- train-mode BatchNorm in one launch per direction, small per-channel extents ----------------------------------------------
 // One workgroup per channel: its N rows of HW floats (stride C*HW) are <= 64 KB, so passes two and three hit L1 / L2.  Used when
 // N*HW <= 16384 and the channel count alone fills the chip (layer3 / layer4 of the ResNets, the inner generator layers); the
@@ -1057,10 +881,322 @@ __global__ __launch_bounds__(256) void bn_train_bwd_reg_kernel(const float* __re
     }
 }
 
-// ---- InstanceNorm2d with the instance in registers (HW % 4 == 0, at most 8 float4 per lane — every map of the networks here up to
-// 128 x 64): the loop kernels above walk the instance three times (twice in the backward) with one load in flight per lane; here
-// each lane loads its U units of every operand together, forms the statistics / sums from registers and writes the results, so
-// the launch costs one memory round trip instead of 3 * U.  Same per-lane order and reductions as the loop kernels: same values.
+// ---- one row of HW contiguous floats: InstanceNorm2d and both halves of the IBN layer ----------------------------------------------
+// A row (n, c) is <= 32 KB for every map of the networks here.  LANES = 16 / 32 / 64 lanes per row (several rows per wave for the
+// small maps, shuffles only), 256: one workgroup per row.  Two forms of each direction, the same per-lane summation order and the
+// same reduction in both, so the same values:
+//   U == 0  loops: the row is walked three times (twice in the backward), passes two and three hit L1 / L2;
+//   U  > 0  registers (HW % 4 == 0, at most U <= 8 float4 per lane): each lane loads its U units of every operand together, forms
+//           the statistics / sums from registers and writes the results — one memory round trip instead of 3 * U.  One buffer
+//           resource per operand over the WHOLE tensor (a wave may hold several rows, a resource must be wave-uniform); lanes
+//           past the row carry the offset NOOB: their loads return zeros, their stores are dropped.
+// Statistics: mean, then the centred sum of squares (two-pass, biased variance).
+// A row either forms its own statistics / sums (an InstanceNorm instance) or takes its channel's (a BatchNorm row of the IBN layer):
+enum { IBN_ROW_IN = 0, IBN_ROW_BN_TRAIN = 1, IBN_ROW_BN_EVAL = 2 };
+
+template <int LANES>
+__device__ __forceinline__ float in_reduce(float v, float* red) {
+    // LANES <= 64: butterfly inside the aligned lane group (several rows share a wave); 256: the whole workgroup
+#pragma unroll
+    for (int off = (LANES < 64 ? LANES : 64) / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    if (LANES <= 64) return v;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0) red[wid] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// byte offsets of lane t's U float4 units of the row that starts at element `row`
+template <int LANES, int U>
+__device__ __forceinline__ void row_unit_offsets(unsigned (&off)[U], int64_t row, int t, int HW) {
+#pragma unroll
+    for (int j = 0; j < U; ++j) off[j] = t + LANES * j < (HW >> 2) ? ((unsigned)row + 4u * (unsigned)(t + LANES * j)) * 4u : NOOB;
+}
+
+// y = act(gamma[c] * (x - mu) * is + beta[c] + res).  own_stats: mu / is are formed here and written to mean_out / invstd_out;
+// otherwise they are given.  own_stats is uniform over the lane group (LANES == 256: the workgroup).
+template <int LANES, int U>
+__device__ __forceinline__ void norm_row_fwd(const float* __restrict__ x, const float* __restrict__ res, float* __restrict__ y,
+                                             unsigned bytes, int64_t row, int HW, int t, float* red, bool own_stats, float mu,
+                                             float is, float eps, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                             int c, int act, float slope, float* __restrict__ mean_out,
+                                             float* __restrict__ invstd_out) {
+    if constexpr (U > 0) {
+        const nrsrc_t rx = n_rsrc(x, bytes), ry = n_rsrc(y, bytes), rr = n_rsrc(res ? res : x, res ? bytes : 0u);
+        unsigned off[U];
+        row_unit_offsets<LANES, U>(off, row, t, HW);
+        float4 a[U], r[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) a[j] = n_load4(rx, off[j]);
+        if (res) {                                               // uniform; in flight behind x while the statistics are formed
+#pragma unroll
+            for (int j = 0; j < U; ++j) r[j] = n_load4(rr, off[j]);
+        }
+        if (own_stats) {
+            float s = 0.f;
+#pragma unroll
+            for (int j = 0; j < U; ++j) s += (a[j].x + a[j].y) + (a[j].z + a[j].w);
+            mu = in_reduce<LANES>(s, red) / (float)HW;
+            float q = 0.f;
+#pragma unroll
+            for (int j = 0; j < U; ++j) {
+                const float d0 = a[j].x - mu, d1 = a[j].y - mu, d2 = a[j].z - mu, d3 = a[j].w - mu;
+                const float e = (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+                q += off[j] != NOOB ? e : 0.f;
+            }
+            is = rsqrtf(in_reduce<LANES>(q, red) / (float)HW + eps);
+            if (t == 0) {
+                *mean_out = mu;
+                *invstd_out = is;
+            }
+        }
+        const float gs = (gamma ? gamma[c] : 1.f) * is;
+        const float sh = (beta ? beta[c] : 0.f) - mu * gs;
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            float4 o;
+            o.x = a[j].x * gs + sh; o.y = a[j].y * gs + sh; o.z = a[j].z * gs + sh; o.w = a[j].w * gs + sh;
+            if (res) { o.x += r[j].x; o.y += r[j].y; o.z += r[j].z; o.w += r[j].w; }
+            o.x = rg_apply_act(o.x, act, slope); o.y = rg_apply_act(o.y, act, slope);
+            o.z = rg_apply_act(o.z, act, slope); o.w = rg_apply_act(o.w, act, slope);
+            n_store4(ry, off[j], o);
+        }
+    } else {
+        constexpr int T = LANES;
+        const float* xp = x + row;
+        const bool vec = (HW & 3) == 0;
+        const int nv = HW >> 2;
+        if (own_stats) {
+            float s = 0.f;
+            if (vec) {
+                for (int i = t; i < nv; i += T) {
+                    const float4 v = reinterpret_cast<const float4*>(xp)[i];
+                    s += (v.x + v.y) + (v.z + v.w);
+                }
+            } else {
+                for (int i = t; i < HW; i += T) s += xp[i];
+            }
+            mu = in_reduce<LANES>(s, red) / (float)HW;
+            float q = 0.f;
+            if (vec) {
+                for (int i = t; i < nv; i += T) {
+                    const float4 v = reinterpret_cast<const float4*>(xp)[i];
+                    const float d0 = v.x - mu, d1 = v.y - mu, d2 = v.z - mu, d3 = v.w - mu;
+                    q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+                }
+            } else {
+                for (int i = t; i < HW; i += T) {
+                    const float d = xp[i] - mu;
+                    q += d * d;
+                }
+            }
+            is = rsqrtf(in_reduce<LANES>(q, red) / (float)HW + eps);
+            if (t == 0) {
+                *mean_out = mu;
+                *invstd_out = is;
+            }
+        }
+        const float gs = (gamma ? gamma[c] : 1.f) * is;
+        const float sh = (beta ? beta[c] : 0.f) - mu * gs;
+        float* yp = y + row;
+        const float* rp = res ? res + row : nullptr;
+        if (vec) {
+            for (int i = t; i < nv; i += T) {
+                const float4 v = reinterpret_cast<const float4*>(xp)[i];
+                float4 o;
+                o.x = v.x * gs + sh; o.y = v.y * gs + sh; o.z = v.z * gs + sh; o.w = v.w * gs + sh;
+                if (rp) {
+                    const float4 r = reinterpret_cast<const float4*>(rp)[i];
+                    o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;
+                }
+                o.x = rg_apply_act(o.x, act, slope); o.y = rg_apply_act(o.y, act, slope);
+                o.z = rg_apply_act(o.z, act, slope); o.w = rg_apply_act(o.w, act, slope);
+                reinterpret_cast<float4*>(yp)[i] = o;
+            }
+        } else {
+            for (int i = t; i < HW; i += T) {
+                float o = xp[i] * gs + sh;
+                if (rp) o += rp[i];
+                yp[i] = rg_apply_act(o, act, slope);
+            }
+        }
+    }
+}
+
+// g = dy * act'(y); s1 = sum g, s2 = sum g * xhat; dx = gamma[c] * is * (g - a - (x - mu) * b); dres = g.  `kind` (uniform over the
+// lane group) says where a and b come from and whether s1 / s2 are written:
+//   IBN_ROW_IN        a = s1 / HW, b = s2 / HW * is from the row's own sums; s1 / s2 written (per instance, for the affine gradients)
+//   IBN_ROW_BN_TRAIN  a, b given (the channel sums); nothing written
+//   IBN_ROW_BN_EVAL   a = b = 0 given (running statistics: dx needs no sum); s1 / s2 written, gathered in the same pass as dx
+// dx, dres and sdx_out (the sum of dx: the bias gradient of a convolution in front) may be NULL.
+template <int LANES, int U>
+__device__ __forceinline__ void norm_row_bwd(const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ yact,
+                                             float* __restrict__ dx, float* __restrict__ dres, unsigned bytes, int64_t row, int HW,
+                                             int t, float* red, int kind, float mu, float is, float a, float b,
+                                             const float* __restrict__ gamma, int c, int act, float slope,
+                                             float* __restrict__ s1_out, float* __restrict__ s2_out, float* __restrict__ sdx_out) {
+    const bool has_act = act != RG_ACT_NONE;
+    float s1 = 0.f, s2 = 0.f, sdx = 0.f;
+    if constexpr (U > 0) {
+        const nrsrc_t rx = n_rsrc(x, bytes), rg = n_rsrc(dy, bytes), ry = n_rsrc(has_act ? yact : dy, has_act ? bytes : 0u);
+        const nrsrc_t rdx = n_rsrc(dx ? dx : dres, dx ? bytes : 0u), rdr = n_rsrc(dres ? dres : dx, dres ? bytes : 0u);
+        unsigned off[U];
+        row_unit_offsets<LANES, U>(off, row, t, HW);
+        float4 g[U], v[U], yv[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            g[j] = n_load4(rg, off[j]);
+            v[j] = n_load4(rx, off[j]);
+            if (has_act) yv[j] = n_load4(ry, off[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < U; ++j) {                            // as the units arrive
+            if (has_act) {
+                g[j].x *= act_grad_from_out(yv[j].x, act, slope); g[j].y *= act_grad_from_out(yv[j].y, act, slope);
+                g[j].z *= act_grad_from_out(yv[j].z, act, slope); g[j].w *= act_grad_from_out(yv[j].w, act, slope);
+            }
+            if (kind != IBN_ROW_BN_TRAIN) {                      // lanes past the row hold g = 0
+                s1 += (g[j].x + g[j].y) + (g[j].z + g[j].w);
+                s2 += (g[j].x * (v[j].x - mu) + g[j].y * (v[j].y - mu)) + (g[j].z * (v[j].z - mu) + g[j].w * (v[j].w - mu));
+            }
+        }
+        if (kind != IBN_ROW_BN_TRAIN) {
+            s1 = in_reduce<LANES>(s1, red);
+            s2 = in_reduce<LANES>(s2, red) * is;
+            if (t == 0) {
+                *s1_out = s1;
+                *s2_out = s2;
+            }
+            if (kind == IBN_ROW_IN) {
+                a = s1 / (float)HW;
+                b = s2 / (float)HW * is;
+            }
+        }
+        const float gs = (gamma ? gamma[c] : 1.f) * is;
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            if (dres) n_store4(rdr, off[j], g[j]);
+            if (dx) {
+                float4 o;
+                o.x = gs * (g[j].x - a - (v[j].x - mu) * b); o.y = gs * (g[j].y - a - (v[j].y - mu) * b);
+                o.z = gs * (g[j].z - a - (v[j].z - mu) * b); o.w = gs * (g[j].w - a - (v[j].w - mu) * b);
+                n_store4(rdx, off[j], o);
+                sdx += off[j] != NOOB ? (o.x + o.y) + (o.z + o.w) : 0.f;
+            }
+        }
+    } else {
+        constexpr int T = LANES;
+        const float* xp = x + row;
+        const float* gp = dy + row;
+        const float* yp = has_act ? yact + row : nullptr;
+        float* dxp = dx ? dx + row : nullptr;
+        float* drp = dres ? dres + row : nullptr;
+        const bool vec = (HW & 3) == 0;
+        const int nv = HW >> 2;
+        auto grad4 = [&](int i) {
+            float4 g = reinterpret_cast<const float4*>(gp)[i];
+            if (yp) {
+                const float4 yv = reinterpret_cast<const float4*>(yp)[i];
+                g.x *= act_grad_from_out(yv.x, act, slope); g.y *= act_grad_from_out(yv.y, act, slope);
+                g.z *= act_grad_from_out(yv.z, act, slope); g.w *= act_grad_from_out(yv.w, act, slope);
+            }
+            return g;
+        };
+        auto grad1 = [&](int i) { return yp ? gp[i] * act_grad_from_out(yp[i], act, slope) : gp[i]; };
+        auto sums4 = [&](int i, const float4& g) {
+            const float4 v = reinterpret_cast<const float4*>(xp)[i];
+            s1 += (g.x + g.y) + (g.z + g.w);
+            s2 += (g.x * (v.x - mu) + g.y * (v.y - mu)) + (g.z * (v.z - mu) + g.w * (v.w - mu));
+        };
+        auto sums1 = [&](int i, float g) {
+            s1 += g;
+            s2 += g * (xp[i] - mu);
+        };
+        auto reduce_sums = [&] {
+            s1 = in_reduce<LANES>(s1, red);
+            s2 = in_reduce<LANES>(s2, red) * is;
+            if (t == 0) {
+                *s1_out = s1;
+                *s2_out = s2;
+            }
+        };
+        if (kind == IBN_ROW_IN) {
+            if (vec) {
+                for (int i = t; i < nv; i += T) sums4(i, grad4(i));
+            } else {
+                for (int i = t; i < HW; i += T) sums1(i, grad1(i));
+            }
+            reduce_sums();
+            a = s1 / (float)HW;
+            b = s2 / (float)HW * is;
+        }
+        const float gs = (gamma ? gamma[c] : 1.f) * is;
+        if (vec) {
+            for (int i = t; i < nv; i += T) {
+                const float4 g = grad4(i);
+                if (drp) reinterpret_cast<float4*>(drp)[i] = g;
+                if (dxp) {
+                    const float4 v = reinterpret_cast<const float4*>(xp)[i];
+                    float4 o;
+                    o.x = gs * (g.x - a - (v.x - mu) * b); o.y = gs * (g.y - a - (v.y - mu) * b);
+                    o.z = gs * (g.z - a - (v.z - mu) * b); o.w = gs * (g.w - a - (v.w - mu) * b);
+                    reinterpret_cast<float4*>(dxp)[i] = o;
+                    sdx += (o.x + o.y) + (o.z + o.w);
+                }
+                if (kind == IBN_ROW_BN_EVAL) sums4(i, g);
+            }
+        } else {
+            for (int i = t; i < HW; i += T) {
+                const float g = grad1(i);
+                if (drp) drp[i] = g;
+                if (dxp) {
+                    const float o = gs * (g - a - (xp[i] - mu) * b);
+                    dxp[i] = o;
+                    sdx += o;
+                }
+                if (kind == IBN_ROW_BN_EVAL) sums1(i, g);
+            }
+        }
+        if (kind == IBN_ROW_BN_EVAL) reduce_sums();
+    }
+    if (sdx_out) {                                               // uniform
+        sdx = in_reduce<LANES>(sdx, red);
+        if (t == 0) *sdx_out = sdx;
+    }
+}
+
+// ---- InstanceNorm2d in one launch per direction: every lane group is one IBN_ROW_IN row (instance) -----------------------------------
+template <int LANES>
+__global__ __launch_bounds__(256) void instnorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                           const float* __restrict__ beta, const float* __restrict__ res,
+                                                           float* __restrict__ y, float* __restrict__ mean_out,
+                                                           float* __restrict__ invstd_out, int NC, int C, int HW, float eps,
+                                                           int act, float slope) {
+    __shared__ float red[4];
+    const int inst = (int)blockIdx.x * (256 / LANES) + (int)threadIdx.x / LANES;
+    if (inst >= NC) return;                                   // whole lane groups leave (LANES == 256: never taken, grid = NC)
+    norm_row_fwd<LANES, 0>(x, res, y, 0u, (int64_t)inst * HW, HW, (int)threadIdx.x % LANES, red, true, 0.f, 0.f, eps, gamma, beta,
+                           inst % C, act, slope, mean_out + inst, invstd_out + inst);
+}
+
+// sum_dy / sum_dy_xhat: per instance, for the affine gradients; sum_dx (may be NULL): the per-instance sums of dx
+template <int LANES>
+__global__ __launch_bounds__(256) void instnorm_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+                                                           const float* __restrict__ yact, const float* __restrict__ mean,
+                                                           const float* __restrict__ invstd, const float* __restrict__ gamma,
+                                                           float* __restrict__ dx, float* __restrict__ dres,
+                                                           float* __restrict__ sum_dy, float* __restrict__ sum_dy_xhat,
+                                                           float* __restrict__ sum_dx, int NC, int C, int HW, int act,
+                                                           float slope) {
+    __shared__ float red[4];
+    const int inst = (int)blockIdx.x * (256 / LANES) + (int)threadIdx.x / LANES;
+    if (inst >= NC) return;
+    norm_row_bwd<LANES, 0>(x, dy, yact, dx, dres, 0u, (int64_t)inst * HW, HW, (int)threadIdx.x % LANES, red, IBN_ROW_IN, mean[inst],
+                           invstd[inst], 0.f, 0.f, gamma, inst % C, act, slope, sum_dy + inst, sum_dy_xhat + inst,
+                           sum_dx ? sum_dx + inst : nullptr);
+}
+
 template <int LANES, int U>
 __global__ __launch_bounds__(256) void instnorm_fwd_reg_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, const float* __restrict__ res,
@@ -1070,47 +1206,8 @@ __global__ __launch_bounds__(256) void instnorm_fwd_reg_kernel(const float* __re
     __shared__ float red[4];
     const int inst = (int)blockIdx.x * (256 / LANES) + (int)threadIdx.x / LANES;
     if (inst >= NC) return;
-    const int t = (int)threadIdx.x % LANES;
-    const int nv = HW >> 2;
-    const nrsrc_t rx = n_rsrc(x, bytes), ry = n_rsrc(y, bytes), rr = n_rsrc(res ? res : x, res ? bytes : 0u);
-    unsigned off[U];
-#pragma unroll
-    for (int j = 0; j < U; ++j) off[j] = t + LANES * j < nv ? ((unsigned)inst * (unsigned)HW + 4u * (unsigned)(t + LANES * j)) * 4u : NOOB;
-    float4 a[U], r[U];
-#pragma unroll
-    for (int j = 0; j < U; ++j) a[j] = n_load4(rx, off[j]);
-    if (res) {
-#pragma unroll
-        for (int j = 0; j < U; ++j) r[j] = n_load4(rr, off[j]);
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < U; ++j) s += (a[j].x + a[j].y) + (a[j].z + a[j].w);
-    const float mu = in_reduce<LANES>(s, red) / (float)HW;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-        const float d0 = a[j].x - mu, d1 = a[j].y - mu, d2 = a[j].z - mu, d3 = a[j].w - mu;
-        const float e = (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-        q += off[j] != NOOB ? e : 0.f;
-    }
-    const float is = rsqrtf(in_reduce<LANES>(q, red) / (float)HW + eps);
-    if (t == 0) {
-        mean_out[inst] = mu;
-        invstd_out[inst] = is;
-    }
-    const int c = inst % C;
-    const float gs = (gamma ? gamma[c] : 1.f) * is;
-    const float sh = (beta ? beta[c] : 0.f) - mu * gs;
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-        float4 o;
-        o.x = a[j].x * gs + sh; o.y = a[j].y * gs + sh; o.z = a[j].z * gs + sh; o.w = a[j].w * gs + sh;
-        if (res) { o.x += r[j].x; o.y += r[j].y; o.z += r[j].z; o.w += r[j].w; }
-        o.x = rg_apply_act(o.x, act, slope); o.y = rg_apply_act(o.y, act, slope);
-        o.z = rg_apply_act(o.z, act, slope); o.w = rg_apply_act(o.w, act, slope);
-        n_store4(ry, off[j], o);
-    }
+    norm_row_fwd<LANES, U>(x, res, y, bytes, (int64_t)inst * HW, HW, (int)threadIdx.x % LANES, red, true, 0.f, 0.f, eps, gamma, beta,
+                           inst % C, act, slope, mean_out + inst, invstd_out + inst);
 }
 
 template <int LANES, int U>
@@ -1124,56 +1221,9 @@ __global__ __launch_bounds__(256) void instnorm_bwd_reg_kernel(const float* __re
     __shared__ float red[4];
     const int inst = (int)blockIdx.x * (256 / LANES) + (int)threadIdx.x / LANES;
     if (inst >= NC) return;
-    const int t = (int)threadIdx.x % LANES;
-    const int nv = HW >> 2;
-    const bool has_act = act != RG_ACT_NONE;
-    const nrsrc_t rx = n_rsrc(x, bytes), rg = n_rsrc(dy, bytes), ry = n_rsrc(has_act ? yact : dy, has_act ? bytes : 0u);
-    const nrsrc_t rdx = n_rsrc(dx ? dx : dres, dx ? bytes : 0u), rdr = n_rsrc(dres ? dres : dx, dres ? bytes : 0u);
-    const float mu = mean[inst], is = invstd[inst];
-    unsigned off[U];
-#pragma unroll
-    for (int j = 0; j < U; ++j) off[j] = t + LANES * j < nv ? ((unsigned)inst * (unsigned)HW + 4u * (unsigned)(t + LANES * j)) * 4u : NOOB;
-    float4 g[U], v[U], yv[U];
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-        g[j] = n_load4(rg, off[j]);
-        v[j] = n_load4(rx, off[j]);
-        if (has_act) yv[j] = n_load4(ry, off[j]);
-    }
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-        if (has_act) {
-            g[j].x *= act_grad_from_out(yv[j].x, act, slope); g[j].y *= act_grad_from_out(yv[j].y, act, slope);
-            g[j].z *= act_grad_from_out(yv[j].z, act, slope); g[j].w *= act_grad_from_out(yv[j].w, act, slope);
-        }
-        s1 += (g[j].x + g[j].y) + (g[j].z + g[j].w);
-        s2 += (g[j].x * (v[j].x - mu) + g[j].y * (v[j].y - mu)) + (g[j].z * (v[j].z - mu) + g[j].w * (v[j].w - mu));
-    }
-    s1 = in_reduce<LANES>(s1, red);
-    s2 = in_reduce<LANES>(s2, red) * is;
-    if (t == 0) {
-        sum_dy[inst] = s1;
-        sum_dy_xhat[inst] = s2;
-    }
-    const float gs = (gamma ? gamma[inst % C] : 1.f) * is;
-    const float a = s1 / (float)HW, b = s2 / (float)HW * is;
-    float sdx = 0.f;
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-        if (dres) n_store4(rdr, off[j], g[j]);
-        if (dx) {
-            float4 o;
-            o.x = gs * (g[j].x - a - (v[j].x - mu) * b); o.y = gs * (g[j].y - a - (v[j].y - mu) * b);
-            o.z = gs * (g[j].z - a - (v[j].z - mu) * b); o.w = gs * (g[j].w - a - (v[j].w - mu) * b);
-            n_store4(rdx, off[j], o);
-            sdx += off[j] != NOOB ? (o.x + o.y) + (o.z + o.w) : 0.f;
-        }
-    }
-    if (sum_dx) {
-        sdx = in_reduce<LANES>(sdx, red);
-        if (t == 0) sum_dx[inst] = sdx;
-    }
+    norm_row_bwd<LANES, U>(x, dy, yact, dx, dres, bytes, (int64_t)inst * HW, HW, (int)threadIdx.x % LANES, red, IBN_ROW_IN, mean[inst],
+                           invstd[inst], 0.f, 0.f, gamma, inst % C, act, slope, sum_dy + inst, sum_dy_xhat + inst,
+                           sum_dx ? sum_dx + inst : nullptr);
 }
 
 // out[c] = sum over n and the pixels of dy[n][c][.] — the bias gradient of a convolution / linear layer — in ONE launch when a
@@ -1374,6 +1424,22 @@ extern "C" int rg_rows_sum_pair(const float* a, const float* b, float* out_a, fl
 // development switch: RG_BN_REG=0 keeps the loop kernels (A/B timing)
 static const bool g_bn_reg = rg::env_int("RG_BN_REG", 1) != 0;
 
+// The templated kernels exist for fixed lists of (lanes per row, float4 per lane) pairs; units = 0 are the loop kernels.
+// with_lanes_units finds the runtime pair in a list and calls f with it as two std::integral_constant; false: not in the list.
+template <int L, int U>
+struct LU {};
+template <class... P>
+struct LUList {};
+using BnUnits = LUList<LU<256, 1>, LU<256, 2>, LU<256, 4>, LU<256, 8>, LU<256, 16>>;      // one workgroup per channel
+using InPairs = LUList<LU<16, 0>, LU<16, 1>, LU<16, 2>, LU<32, 0>, LU<32, 1>, LU<32, 2>, LU<64, 0>, LU<64, 1>, LU<64, 2>, LU<64, 4>,
+                       LU<64, 8>, LU<256, 0>, LU<256, 1>, LU<256, 2>, LU<256, 4>, LU<256, 8>>;
+using IbnPairs = LUList<LU<16, 0>, LU<16, 2>, LU<32, 0>, LU<32, 2>, LU<64, 0>, LU<64, 2>, LU<64, 8>, LU<256, 0>, LU<256, 8>>;
+
+template <class F, int... L, int... U>
+static bool with_lanes_units(LUList<LU<L, U>...>, int lanes, int units, F&& f) {
+    return ((lanes == L && units == U && (f(std::integral_constant<int, L>{}, std::integral_constant<int, U>{}), true)) || ...);
+}
+
 extern "C" size_t rg_bn_train_fused_ok(int N, int C, int HW) {
     return (int64_t)N * HW <= 16384 && C >= 128 ? 1 : 0;
 }
@@ -1385,20 +1451,12 @@ extern "C" int rg_bn_train_fwd_fused(const float* x, const float* gamma, const f
     RG_REQUIRE((int64_t)N * HW < (1ll << 30), "rg_bn_train_fwd_fused: N*HW too large");
     rg::ProfScope prof(rg::FAM_NORM, stream, 0.0, (residual ? 12.0 : 8.0) * N * (double)C * HW);
     const unsigned bytes = (unsigned)((int64_t)N * C * HW * 4);
-#define RG_BNF(U_)                                                                                                             \
-    hipLaunchKernelGGL(bn_train_fwd_reg_kernel<U_>, dim3(C), dim3(256), 0, stream, x, gamma, beta, residual, y, mean, invstd,   \
-                       running_mean, running_var, N, C, HW, eps, momentum, act, slope, bytes)
-    switch (g_bn_reg ? bn_reg_units(N, C, HW) : 0) {
-        case 1: RG_BNF(1); break;
-        case 2: RG_BNF(2); break;
-        case 4: RG_BNF(4); break;
-        case 8: RG_BNF(8); break;
-        case 16: RG_BNF(16); break;
-        default:
-            hipLaunchKernelGGL(bn_train_fwd_fused_kernel, dim3(C), dim3(256), 0, stream, x, gamma, beta, residual, y, mean, invstd,
-                               running_mean, running_var, N, C, HW, eps, momentum, act, slope);
-    }
-#undef RG_BNF
+    if (!with_lanes_units(BnUnits{}, 256, g_bn_reg ? bn_reg_units(N, C, HW) : 0, [&](auto, auto U) {
+            hipLaunchKernelGGL(bn_train_fwd_reg_kernel<U>, dim3(C), dim3(256), 0, stream, x, gamma, beta, residual, y, mean, invstd,
+                               running_mean, running_var, N, C, HW, eps, momentum, act, slope, bytes);
+        }))
+        hipLaunchKernelGGL(bn_train_fwd_fused_kernel, dim3(C), dim3(256), 0, stream, x, gamma, beta, residual, y, mean, invstd,
+                           running_mean, running_var, N, C, HW, eps, momentum, act, slope);
     return rg::check_launch("rg_bn_train_fwd_fused");
 }
 
@@ -1410,20 +1468,12 @@ extern "C" int rg_bn_train_bwd_fused(const float* x, const float* dy, const floa
     RG_REQUIRE((int64_t)N * HW < (1ll << 30), "rg_bn_train_bwd_fused: N*HW too large");
     rg::ProfScope prof(rg::FAM_NORM, stream, 0.0, ((act ? 12.0 : 8.0) + (dx ? 4.0 : 0.0) + (dres ? 4.0 : 0.0)) * N * (double)C * HW);
     const unsigned bytes = (unsigned)((int64_t)N * C * HW * 4);
-#define RG_BNB(U_)                                                                                                             \
-    hipLaunchKernelGGL(bn_train_bwd_reg_kernel<U_>, dim3(C), dim3(256), 0, stream, x, dy, y_act, mean, invstd, gamma, dx, dres,  \
-                       sum_dy, sum_dy_xhat, N, C, HW, act, slope, bytes)
-    switch (g_bn_reg ? bn_reg_units(N, C, HW) : 0) {
-        case 1: RG_BNB(1); break;
-        case 2: RG_BNB(2); break;
-        case 4: RG_BNB(4); break;
-        case 8: RG_BNB(8); break;
-        case 16: RG_BNB(16); break;
-        default:
-            hipLaunchKernelGGL(bn_train_bwd_fused_kernel, dim3(C), dim3(256), 0, stream, x, dy, y_act, mean, invstd, gamma, dx, dres,
-                               sum_dy, sum_dy_xhat, N, C, HW, act, slope);
-    }
-#undef RG_BNB
+    if (!with_lanes_units(BnUnits{}, 256, g_bn_reg ? bn_reg_units(N, C, HW) : 0, [&](auto, auto U) {
+            hipLaunchKernelGGL(bn_train_bwd_reg_kernel<U>, dim3(C), dim3(256), 0, stream, x, dy, y_act, mean, invstd, gamma, dx, dres,
+                               sum_dy, sum_dy_xhat, N, C, HW, act, slope, bytes);
+        }))
+        hipLaunchKernelGGL(bn_train_bwd_fused_kernel, dim3(C), dim3(256), 0, stream, x, dy, y_act, mean, invstd, gamma, dx, dres,
+                           sum_dy, sum_dy_xhat, N, C, HW, act, slope);
     return rg::check_launch("rg_bn_train_bwd_fused");
 }
 
@@ -1436,6 +1486,13 @@ static int in_lanes(int HW) {
     return 64;
 }
 
+// float4 per lane (1, 2, 4, 8) of the register rows for a tensor of `elems` floats, 0 = the loop rows
+static int row_reg_units(int HW, int lanes, int64_t elems) {
+    if (!g_bn_reg || (HW & 3) || elems * 4 >= (1ll << 31)) return 0;
+    const int per = ((HW >> 2) + lanes - 1) / lanes;
+    return per <= 1 ? 1 : per <= 2 ? 2 : per <= 4 ? 4 : per <= 8 ? 8 : 0;
+}
+
 // InstanceNorm2d forward: y = act(gamma[c] * (x - mean[n,c]) * invstd[n,c] + beta[c] + residual); mean / invstd [N*C] are kept for
 // the backward.  One launch.
 extern "C" int rg_instnorm_fwd(const float* x, const float* gamma, const float* beta, const float* residual, float* y,
@@ -1445,33 +1502,19 @@ extern "C" int rg_instnorm_fwd(const float* x, const float* gamma, const float* 
     RG_REQUIRE((int64_t)N * C < (1ll << 31), "rg_instnorm_fwd: N*C exceeds 2^31");
     const int NC = N * C;
     rg::ProfScope prof(rg::FAM_NORM, stream, 0.0, (residual ? 12.0 : 8.0) * (double)NC * HW);
-    const int lanes = in_lanes(HW);
-    const int per = (HW & 3) ? 0 : ((HW >> 2) + lanes - 1) / lanes;
-    if (g_bn_reg && per >= 1 && per <= 8 && (int64_t)NC * HW * 4 < (1ll << 31)) {
-        const unsigned bytes = (unsigned)((int64_t)NC * HW * 4);
-        const int U = per <= 1 ? 1 : per <= 2 ? 2 : per <= 4 ? 4 : 8;
-#define RG_INF(L_, U_)                                                                                                             \
-    case L_ * 16 + U_:                                                                                                             \
-        hipLaunchKernelGGL((instnorm_fwd_reg_kernel<L_, U_>), dim3(rg::cdiv(NC, 256 / L_)), dim3(256), 0, stream, x, gamma, beta,    \
-                           residual, y, mean, invstd, NC, C, HW, eps, act, slope, bytes);                                          \
-        break
-        switch (lanes * 16 + U) {
-            RG_INF(16, 1); RG_INF(16, 2); RG_INF(32, 1); RG_INF(32, 2); RG_INF(64, 1); RG_INF(64, 2); RG_INF(64, 4); RG_INF(64, 8);
-            RG_INF(256, 1); RG_INF(256, 2); RG_INF(256, 4); RG_INF(256, 8);
-            default: rg::set_error("rg_instnorm_fwd: no register kernel for %d lanes x %d units", lanes, U); return RG_ERR_INVALID;
-        }
-#undef RG_INF
-        return rg::check_launch("rg_instnorm_fwd");
-    }
-    switch (lanes) {
-        case 16: hipLaunchKernelGGL(instnorm_fwd_kernel<16>, dim3(rg::cdiv(NC, 16)), dim3(256), 0, stream, x, gamma, beta, residual, y,
-                                    mean, invstd, NC, C, HW, eps, act, slope); break;
-        case 32: hipLaunchKernelGGL(instnorm_fwd_kernel<32>, dim3(rg::cdiv(NC, 8)), dim3(256), 0, stream, x, gamma, beta, residual, y,
-                                    mean, invstd, NC, C, HW, eps, act, slope); break;
-        case 64: hipLaunchKernelGGL(instnorm_fwd_kernel<64>, dim3(rg::cdiv(NC, 4)), dim3(256), 0, stream, x, gamma, beta, residual, y,
-                                    mean, invstd, NC, C, HW, eps, act, slope); break;
-        default: hipLaunchKernelGGL(instnorm_fwd_kernel<256>, dim3(NC), dim3(256), 0, stream, x, gamma, beta, residual, y, mean,
-                                    invstd, NC, C, HW, eps, act, slope);
+    const int lanes = in_lanes(HW), units = row_reg_units(HW, lanes, (int64_t)NC * HW);
+    const unsigned bytes = units ? (unsigned)((int64_t)NC * HW * 4) : 0u;
+    if (!with_lanes_units(InPairs{}, lanes, units, [&](auto L, auto U) {
+            const dim3 grid(rg::cdiv(NC, 256 / L));
+            if constexpr (U > 0)
+                hipLaunchKernelGGL((instnorm_fwd_reg_kernel<L, U>), grid, dim3(256), 0, stream, x, gamma, beta, residual, y, mean,
+                                   invstd, NC, C, HW, eps, act, slope, bytes);
+            else
+                hipLaunchKernelGGL(instnorm_fwd_kernel<L>, grid, dim3(256), 0, stream, x, gamma, beta, residual, y, mean, invstd, NC,
+                                   C, HW, eps, act, slope);
+        })) {
+        rg::set_error("rg_instnorm_fwd: no kernel for %d lanes x %d units", lanes, units);
+        return RG_ERR_INVALID;
     }
     return rg::check_launch("rg_instnorm_fwd");
 }
@@ -1487,33 +1530,19 @@ extern "C" int rg_instnorm_bwd(const float* x, const float* dy, const float* y_a
     RG_REQUIRE((int64_t)N * C < (1ll << 31), "rg_instnorm_bwd: N*C exceeds 2^31");
     const int NC = N * C;
     rg::ProfScope prof(rg::FAM_NORM, stream, 0.0, ((act ? 12.0 : 8.0) + (dx ? 4.0 : 0.0) + (dres ? 4.0 : 0.0)) * (double)NC * HW);
-    const int lanes = in_lanes(HW);
-    const int per = (HW & 3) ? 0 : ((HW >> 2) + lanes - 1) / lanes;
-    if (g_bn_reg && per >= 1 && per <= 8 && (int64_t)NC * HW * 4 < (1ll << 31)) {
-        const unsigned bytes = (unsigned)((int64_t)NC * HW * 4);
-        const int U = per <= 1 ? 1 : per <= 2 ? 2 : per <= 4 ? 4 : 8;
-#define RG_INB(L_, U_)                                                                                                             \
-    case L_ * 16 + U_:                                                                                                             \
-        hipLaunchKernelGGL((instnorm_bwd_reg_kernel<L_, U_>), dim3(rg::cdiv(NC, 256 / L_)), dim3(256), 0, stream, x, dy, y_act,     \
-                           mean, invstd, gamma, dx, dres, sum_dy, sum_dy_xhat, sum_dx, NC, C, HW, act, slope, bytes);              \
-        break
-        switch (lanes * 16 + U) {
-            RG_INB(16, 1); RG_INB(16, 2); RG_INB(32, 1); RG_INB(32, 2); RG_INB(64, 1); RG_INB(64, 2); RG_INB(64, 4); RG_INB(64, 8);
-            RG_INB(256, 1); RG_INB(256, 2); RG_INB(256, 4); RG_INB(256, 8);
-            default: rg::set_error("rg_instnorm_bwd: no register kernel for %d lanes x %d units", lanes, U); return RG_ERR_INVALID;
-        }
-#undef RG_INB
-        return rg::check_launch("rg_instnorm_bwd");
-    }
-    switch (lanes) {
-        case 16: hipLaunchKernelGGL(instnorm_bwd_kernel<16>, dim3(rg::cdiv(NC, 16)), dim3(256), 0, stream, x, dy, y_act, mean, invstd,
-                                    gamma, dx, dres, sum_dy, sum_dy_xhat, sum_dx, NC, C, HW, act, slope); break;
-        case 32: hipLaunchKernelGGL(instnorm_bwd_kernel<32>, dim3(rg::cdiv(NC, 8)), dim3(256), 0, stream, x, dy, y_act, mean, invstd,
-                                    gamma, dx, dres, sum_dy, sum_dy_xhat, sum_dx, NC, C, HW, act, slope); break;
-        case 64: hipLaunchKernelGGL(instnorm_bwd_kernel<64>, dim3(rg::cdiv(NC, 4)), dim3(256), 0, stream, x, dy, y_act, mean, invstd,
-                                    gamma, dx, dres, sum_dy, sum_dy_xhat, sum_dx, NC, C, HW, act, slope); break;
-        default: hipLaunchKernelGGL(instnorm_bwd_kernel<256>, dim3(NC), dim3(256), 0, stream, x, dy, y_act, mean, invstd, gamma, dx,
-                                    dres, sum_dy, sum_dy_xhat, sum_dx, NC, C, HW, act, slope);
+    const int lanes = in_lanes(HW), units = row_reg_units(HW, lanes, (int64_t)NC * HW);
+    const unsigned bytes = units ? (unsigned)((int64_t)NC * HW * 4) : 0u;
+    if (!with_lanes_units(InPairs{}, lanes, units, [&](auto L, auto U) {
+            const dim3 grid(rg::cdiv(NC, 256 / L));
+            if constexpr (U > 0)
+                hipLaunchKernelGGL((instnorm_bwd_reg_kernel<L, U>), grid, dim3(256), 0, stream, x, dy, y_act, mean, invstd, gamma, dx,
+                                   dres, sum_dy, sum_dy_xhat, sum_dx, NC, C, HW, act, slope, bytes);
+            else
+                hipLaunchKernelGGL(instnorm_bwd_kernel<L>, grid, dim3(256), 0, stream, x, dy, y_act, mean, invstd, gamma, dx, dres,
+                                   sum_dy, sum_dy_xhat, sum_dx, NC, C, HW, act, slope);
+        })) {
+        rg::set_error("rg_instnorm_bwd: no kernel for %d lanes x %d units", lanes, units);
+        return RG_ERR_INVALID;
     }
     return rg::check_launch("rg_instnorm_bwd");
 }
@@ -1642,8 +1671,9 @@ extern "C" int rg_fold_chunk(void) { return FOLD_CHUNK; }
 // The reference writes the layer as split -> contiguous x 2 -> two norms -> cat (CC/clustercontrast/models/resnet_ibn_a.py:54-68):
 // six extra passes over the activation per direction.  Here both halves are normalised in place of layout: the only tensors of
 // the activation's size are x, y (forward) and x, dy, y, dx (backward).
-//   row kernels     one lane group (16 / 32 / 64 lanes, or the workgroup) per row (n, c) of HW contiguous floats, as the
-//                   InstanceNorm kernels above, the row in registers when it fits (at most 8 float4 per lane), loops otherwise.  An IN row forms its own statistics / sums (two-pass, biased variance); a BN row
+//   row kernels     one lane group per row (n, c), on the row bodies of the InstanceNorm kernels (norm_row_fwd / norm_row_bwd: the
+//                   same lane counts, the same register and loop forms; only the backward register row is the layer's own,
+//                   ibn_row_bwd_reg).  An IN row forms its own statistics / sums; a BN row
 //                   takes the channel's statistics (running ones in eval mode, the batch ones of the slice-parallel
 //                   bn_stats_partial / bn_bwd_reduce_partial kernels, run over the channel sub-range with the full tensor's
 //                   sample stride, in train mode).  A lane group is one kind of row, so the branches are group-uniform.
@@ -1652,187 +1682,69 @@ extern "C" int rg_fold_chunk(void) { return FOLD_CHUNK; }
 // Backward sums: IN rows write sum g and sum g*xhat per instance, eval-mode BN rows per (n, channel) as well (their dx needs no
 // channel sum, so the row is read once); rows_sum_pair_kernel adds them over n into the four affine gradients.  Train-mode BN
 // channel sums come from the channel workgroups / the slice reduction and ARE dbeta / dgamma.  Fixed summation order, no atomics.
-template <int LANES>
-__device__ __forceinline__ void ibn_row_fwd(const float* __restrict__ xp, float* __restrict__ yp, int HW, int t, float* red,
-                                            bool own_stats, float mu, float is, float eps, float g, float b, int act,
-                                            float* __restrict__ mean_out, float* __restrict__ invstd_out) {
-    constexpr int T = LANES;
-    const bool vec = (HW & 3) == 0;
-    const int nv = HW >> 2;
-    if (own_stats) {                                              // uniform over the lane group (LANES == 256: the workgroup)
-        float s = 0.f;
-        if (vec) {
-            for (int i = t; i < nv; i += T) {
-                const float4 v = reinterpret_cast<const float4*>(xp)[i];
-                s += (v.x + v.y) + (v.z + v.w);
-            }
-        } else {
-            for (int i = t; i < HW; i += T) s += xp[i];
-        }
-        mu = in_reduce<LANES>(s, red) / (float)HW;
-        float q = 0.f;
-        if (vec) {
-            for (int i = t; i < nv; i += T) {
-                const float4 v = reinterpret_cast<const float4*>(xp)[i];
-                const float a = v.x - mu, bb = v.y - mu, c = v.z - mu, d = v.w - mu;
-                q += (a * a + bb * bb) + (c * c + d * d);
-            }
-        } else {
-            for (int i = t; i < HW; i += T) {
-                const float a = xp[i] - mu;
-                q += a * a;
-            }
-        }
-        is = rsqrtf(in_reduce<LANES>(q, red) / (float)HW + eps);
-        if (t == 0) {
-            *mean_out = mu;
-            *invstd_out = is;
-        }
-    }
-    const float gs = g * is;
-    const float sh = b - mu * gs;
-    if (vec) {
-        for (int i = t; i < nv; i += T) {
-            const float4 v = reinterpret_cast<const float4*>(xp)[i];
-            float4 o;
-            o.x = rg_apply_act(v.x * gs + sh, act, 0.f); o.y = rg_apply_act(v.y * gs + sh, act, 0.f);
-            o.z = rg_apply_act(v.z * gs + sh, act, 0.f); o.w = rg_apply_act(v.w * gs + sh, act, 0.f);
-            reinterpret_cast<float4*>(yp)[i] = o;
-        }
-    } else {
-        for (int i = t; i < HW; i += T) yp[i] = rg_apply_act(xp[i] * gs + sh, act, 0.f);
-    }
-}
 
-enum { IBN_ROW_IN = 0, IBN_ROW_BN_TRAIN = 1, IBN_ROW_BN_EVAL = 2 };
-
-// g = dy * act'(y); dx = gs * (g - a - (x - mu) * b).  IN row: a, b from its own sums (first pass); BN train row: a, b given (channel
-// sums); BN eval row: a = b = 0 and the sums are gathered in the same pass.  s1 / s2 are written except for BN train rows.
-template <int LANES>
-__device__ __forceinline__ void ibn_row_bwd(const float* __restrict__ xp, const float* __restrict__ gp, const float* __restrict__ yp,
-                                            float* __restrict__ dxp, int HW, int t, float* red, int kind, float mu, float is,
-                                            float gs, float a, float b, int act, float* __restrict__ s1_out,
-                                            float* __restrict__ s2_out) {
-    constexpr int T = LANES;
-    const bool vec = (HW & 3) == 0;
-    const int nv = HW >> 2;
-    float s1 = 0.f, s2 = 0.f;
-    if (kind == IBN_ROW_IN) {
-        if (vec) {
-            for (int i = t; i < nv; i += T) {
-                float4 g = reinterpret_cast<const float4*>(gp)[i];
-                if (yp) {
-                    const float4 yv = reinterpret_cast<const float4*>(yp)[i];
-                    g.x *= act_grad_from_out(yv.x, act, 0.f); g.y *= act_grad_from_out(yv.y, act, 0.f);
-                    g.z *= act_grad_from_out(yv.z, act, 0.f); g.w *= act_grad_from_out(yv.w, act, 0.f);
-                }
-                const float4 v = reinterpret_cast<const float4*>(xp)[i];
-                s1 += (g.x + g.y) + (g.z + g.w);
-                s2 += (g.x * (v.x - mu) + g.y * (v.y - mu)) + (g.z * (v.z - mu) + g.w * (v.w - mu));
-            }
-        } else {
-            for (int i = t; i < HW; i += T) {
-                float g = gp[i];
-                if (yp) g *= act_grad_from_out(yp[i], act, 0.f);
-                s1 += g;
-                s2 += g * (xp[i] - mu);
-            }
-        }
-        s1 = in_reduce<LANES>(s1, red);
-        s2 = in_reduce<LANES>(s2, red) * is;
-        if (t == 0) {
-            *s1_out = s1;
-            *s2_out = s2;
-        }
-        a = s1 / (float)HW;
-        b = s2 / (float)HW * is;
-        s1 = s2 = 0.f;
-    }
-    if (vec) {
-        for (int i = t; i < nv; i += T) {
-            float4 g = reinterpret_cast<const float4*>(gp)[i];
-            if (yp) {
-                const float4 yv = reinterpret_cast<const float4*>(yp)[i];
-                g.x *= act_grad_from_out(yv.x, act, 0.f); g.y *= act_grad_from_out(yv.y, act, 0.f);
-                g.z *= act_grad_from_out(yv.z, act, 0.f); g.w *= act_grad_from_out(yv.w, act, 0.f);
-            }
-            const float4 v = reinterpret_cast<const float4*>(xp)[i];
-            const float d0 = v.x - mu, d1 = v.y - mu, d2 = v.z - mu, d3 = v.w - mu;
-            float4 o;
-            o.x = gs * (g.x - a - d0 * b); o.y = gs * (g.y - a - d1 * b);
-            o.z = gs * (g.z - a - d2 * b); o.w = gs * (g.w - a - d3 * b);
-            reinterpret_cast<float4*>(dxp)[i] = o;
-            s1 += (g.x + g.y) + (g.z + g.w);
-            s2 += (g.x * d0 + g.y * d1) + (g.z * d2 + g.w * d3);
-        }
-    } else {
-        for (int i = t; i < HW; i += T) {
-            float g = gp[i];
-            if (yp) g *= act_grad_from_out(yp[i], act, 0.f);
-            const float d = xp[i] - mu;
-            dxp[i] = gs * (g - a - d * b);
-            s1 += g;
-            s2 += g * d;
-        }
-    }
-    if (kind == IBN_ROW_BN_EVAL) {
-        s1 = in_reduce<LANES>(s1, red);
-        s2 = in_reduce<LANES>(s2, red) * is;
-        if (t == 0) {
-            *s1_out = s1;
-            *s2_out = s2;
-        }
-    }
-}
-
-// The same two rows with the row in registers (HW % 4 == 0, at most U float4 per lane: every IBN map of the ResNets up to 64 x 32):
-// each operand is loaded once, all loads of a lane in flight together, instead of one load per loop iteration and pass — what
-// instnorm_*_reg_kernel do for the plain InstanceNorm.  Same per-lane order and reductions as the loops above.
+// every row (n, c) of the tensor; BN rows use bn_mean / bn_stat [C - half] (stat_is_var: a variance, eps applied here)
 template <int LANES, int U>
-__device__ __forceinline__ void ibn_row_fwd_reg(const float* __restrict__ xp, float* __restrict__ yp, int HW, int t, float* red,
-                                                bool own_stats, float mu, float is, float eps, float g, float b, int act,
-                                                float* __restrict__ mean_out, float* __restrict__ invstd_out) {
-    const int nv = HW >> 2;
-    float4 a[U];
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-        const int i = t + LANES * j;
-        a[j] = i < nv ? reinterpret_cast<const float4*>(xp)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+__global__ __launch_bounds__(256) void ibn_fwd_rows_kernel(const float* __restrict__ x, const float* __restrict__ in_gamma,
+                                                           const float* __restrict__ in_beta, const float* __restrict__ bn_gamma,
+                                                           const float* __restrict__ bn_beta, const float* __restrict__ bn_mean,
+                                                           const float* __restrict__ bn_stat, float* __restrict__ y,
+                                                           float* __restrict__ in_mean, float* __restrict__ in_invstd, int NC, int C,
+                                                           int half, int HW, int stat_is_var, float in_eps, float bn_eps, int act,
+                                                           unsigned bytes) {
+    __shared__ float red[4];
+    const int row = (int)blockIdx.x * (256 / LANES) + (int)threadIdx.x / LANES;
+    if (row >= NC) return;                                       // whole lane groups leave (LANES == 256: grid = NC)
+    const int n = row / C, c = row - n * C;
+    const bool in_row = c < half;
+    const int pc = in_row ? c : c - half;                        // index of the row's affine parameters (and BN statistics)
+    const int inst = n * half + pc;                              // IN rows only
+    float mu = 0.f, is = 0.f;
+    if (!in_row) {
+        mu = bn_mean[pc];
+        is = bn_stat[pc];
+        if (stat_is_var) is = rsqrtf(is + bn_eps);
     }
-    if (own_stats) {
-        float s = 0.f;
-#pragma unroll
-        for (int j = 0; j < U; ++j) s += (a[j].x + a[j].y) + (a[j].z + a[j].w);
-        mu = in_reduce<LANES>(s, red) / (float)HW;
-        float q = 0.f;
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-            const float d0 = a[j].x - mu, d1 = a[j].y - mu, d2 = a[j].z - mu, d3 = a[j].w - mu;
-            q += t + LANES * j < nv ? (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3) : 0.f;
-        }
-        is = rsqrtf(in_reduce<LANES>(q, red) / (float)HW + eps);
-        if (t == 0) {
-            *mean_out = mu;
-            *invstd_out = is;
-        }
-    }
-    const float gs = g * is;
-    const float sh = b - mu * gs;
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-        const int i = t + LANES * j;
-        float4 o;
-        o.x = rg_apply_act(a[j].x * gs + sh, act, 0.f); o.y = rg_apply_act(a[j].y * gs + sh, act, 0.f);
-        o.z = rg_apply_act(a[j].z * gs + sh, act, 0.f); o.w = rg_apply_act(a[j].w * gs + sh, act, 0.f);
-        if (i < nv) reinterpret_cast<float4*>(yp)[i] = o;
-    }
+    norm_row_fwd<LANES, U>(x, nullptr, y, bytes, (int64_t)row * HW, HW, (int)threadIdx.x % LANES, red, in_row, mu, is, in_eps,
+                           in_row ? in_gamma : bn_gamma, in_row ? in_beta : bn_beta, pc, act, 0.f, in_mean + inst, in_invstd + inst);
 }
 
+// grid = (C - half) BN channel workgroups, then the IN lane groups over the N * half instances
 template <int LANES, int U>
-__device__ __forceinline__ void ibn_row_bwd_reg(const float* __restrict__ xp, const float* __restrict__ gp, const float* __restrict__ yp,
-                                                float* __restrict__ dxp, int HW, int t, float* red, int kind, float mu, float is,
-                                                float gs, float a, float b, int act, float* __restrict__ s1_out,
-                                                float* __restrict__ s2_out) {
+__global__ __launch_bounds__(256) void ibn_train_fwd_fused_kernel(const float* __restrict__ x, const float* __restrict__ in_gamma,
+                                                                  const float* __restrict__ in_beta, const float* __restrict__ bn_gamma,
+                                                                  const float* __restrict__ bn_beta, float* __restrict__ y,
+                                                                  float* __restrict__ in_mean, float* __restrict__ in_invstd,
+                                                                  float* __restrict__ bn_mean, float* __restrict__ bn_invstd,
+                                                                  float* __restrict__ running_mean, float* __restrict__ running_var,
+                                                                  int N, int C, int half, int HW, float in_eps, float bn_eps,
+                                                                  float momentum, int act, unsigned bytes) {
+    __shared__ float red[4];
+    const int cb = C - half;
+    if ((int)blockIdx.x < cb) {                                   // workgroup-uniform
+        bn_channel_fwd(x, bn_gamma, bn_beta, nullptr, y, bn_mean, bn_invstd, running_mean, running_var, N, C, HW, bn_eps, momentum,
+                       act, 0.f, half + (int)blockIdx.x, (int)blockIdx.x, red);
+        return;
+    }
+    const int inst = ((int)blockIdx.x - cb) * (256 / LANES) + (int)threadIdx.x / LANES;
+    if (inst >= N * half) return;
+    const int n = inst / half, c = inst - n * half;
+    norm_row_fwd<LANES, U>(x, nullptr, y, bytes, ((int64_t)n * C + c) * HW, HW, (int)threadIdx.x % LANES, red, true, 0.f, 0.f, in_eps,
+                           in_gamma, in_beta, c, act, 0.f, in_mean + inst, in_invstd + inst);
+}
+
+// The backward register rows of the IBN kernels keep guarded pointer loads: on norm_row_bwd's buffer loads (three operands x 8 units
+// in flight) ibn_train_bwd_fused_kernel<64, 8> needs 113 VGPRs instead of 89 and drops from 5 waves per SIMD to 4.
+template <int LANES, int U>
+__device__ __forceinline__ void ibn_row_bwd_reg(const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ yact,
+                                                float* __restrict__ dx, int64_t row, int HW, int t, float* red, int kind, float mu,
+                                                float is, float a, float b, const float* __restrict__ gamma, int c, int act,
+                                                float* __restrict__ s1_out, float* __restrict__ s2_out) {
+    const float* xp = x + row;
+    const float* gp = dy + row;
+    const float* yp = act != RG_ACT_NONE ? yact + row : nullptr;
+    float* dxp = dx + row;
+    const float gs = (gamma ? gamma[c] : 1.f) * is;
     const int nv = HW >> 2;
     const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 g[U], v[U];
@@ -1876,74 +1788,14 @@ __device__ __forceinline__ void ibn_row_bwd_reg(const float* __restrict__ xp, co
     }
 }
 
-// U = 0: the loop rows; U > 0: the register rows
+// U = 0: the shared loop row; U > 0: the register row above
 template <int LANES, int U>
-__device__ __forceinline__ void ibn_fwd_row(const float* __restrict__ xp, float* __restrict__ yp, int HW, int t, float* red,
-                                            bool own_stats, float mu, float is, float eps, float g, float b, int act,
-                                            float* __restrict__ mean_out, float* __restrict__ invstd_out) {
-    if constexpr (U > 0) ibn_row_fwd_reg<LANES, U>(xp, yp, HW, t, red, own_stats, mu, is, eps, g, b, act, mean_out, invstd_out);
-    else ibn_row_fwd<LANES>(xp, yp, HW, t, red, own_stats, mu, is, eps, g, b, act, mean_out, invstd_out);
-}
-
-template <int LANES, int U>
-__device__ __forceinline__ void ibn_bwd_row(const float* __restrict__ xp, const float* __restrict__ gp, const float* __restrict__ yp,
-                                            float* __restrict__ dxp, int HW, int t, float* red, int kind, float mu, float is, float gs,
-                                            float a, float b, int act, float* __restrict__ s1_out, float* __restrict__ s2_out) {
-    if constexpr (U > 0) ibn_row_bwd_reg<LANES, U>(xp, gp, yp, dxp, HW, t, red, kind, mu, is, gs, a, b, act, s1_out, s2_out);
-    else ibn_row_bwd<LANES>(xp, gp, yp, dxp, HW, t, red, kind, mu, is, gs, a, b, act, s1_out, s2_out);
-}
-
-// every row (n, c) of the tensor; BN rows use bn_mean / bn_stat [C - half] (stat_is_var: a variance, eps applied here)
-template <int LANES, int U>
-__global__ __launch_bounds__(256) void ibn_fwd_rows_kernel(const float* __restrict__ x, const float* __restrict__ in_gamma,
-                                                           const float* __restrict__ in_beta, const float* __restrict__ bn_gamma,
-                                                           const float* __restrict__ bn_beta, const float* __restrict__ bn_mean,
-                                                           const float* __restrict__ bn_stat, float* __restrict__ y,
-                                                           float* __restrict__ in_mean, float* __restrict__ in_invstd, int NC, int C,
-                                                           int half, int HW, int stat_is_var, float in_eps, float bn_eps, int act) {
-    __shared__ float red[4];
-    const int row = (int)blockIdx.x * (256 / LANES) + (int)threadIdx.x / LANES;
-    if (row >= NC) return;                                       // whole lane groups leave (LANES == 256: grid = NC)
-    const int t = (int)threadIdx.x % LANES;
-    const int n = row / C, c = row - n * C;
-    const int64_t base = (int64_t)row * HW;
-    if (c < half) {
-        const int inst = n * half + c;
-        ibn_fwd_row<LANES, U>(x + base, y + base, HW, t, red, true, 0.f, 0.f, in_eps, in_gamma ? in_gamma[c] : 1.f,
-                              in_beta ? in_beta[c] : 0.f, act, in_mean + inst, in_invstd + inst);
-    } else {
-        const int sc = c - half;
-        float is = bn_stat[sc];
-        if (stat_is_var) is = rsqrtf(is + bn_eps);
-        ibn_fwd_row<LANES, U>(x + base, y + base, HW, t, red, false, bn_mean[sc], is, 0.f, bn_gamma ? bn_gamma[sc] : 1.f,
-                              bn_beta ? bn_beta[sc] : 0.f, act, nullptr, nullptr);
-    }
-}
-
-// grid = (C - half) BN channel workgroups, then the IN lane groups over the N * half instances
-template <int LANES, int U>
-__global__ __launch_bounds__(256) void ibn_train_fwd_fused_kernel(const float* __restrict__ x, const float* __restrict__ in_gamma,
-                                                                  const float* __restrict__ in_beta, const float* __restrict__ bn_gamma,
-                                                                  const float* __restrict__ bn_beta, float* __restrict__ y,
-                                                                  float* __restrict__ in_mean, float* __restrict__ in_invstd,
-                                                                  float* __restrict__ bn_mean, float* __restrict__ bn_invstd,
-                                                                  float* __restrict__ running_mean, float* __restrict__ running_var,
-                                                                  int N, int C, int half, int HW, float in_eps, float bn_eps,
-                                                                  float momentum, int act) {
-    __shared__ float red[4];
-    const int cb = C - half;
-    if ((int)blockIdx.x < cb) {                                   // workgroup-uniform
-        bn_channel_fwd(x, bn_gamma, bn_beta, nullptr, y, bn_mean, bn_invstd, running_mean, running_var, N, C, HW, bn_eps, momentum,
-                       act, 0.f, half + (int)blockIdx.x, (int)blockIdx.x, red);
-        return;
-    }
-    const int inst = ((int)blockIdx.x - cb) * (256 / LANES) + (int)threadIdx.x / LANES;
-    if (inst >= N * half) return;
-    const int t = (int)threadIdx.x % LANES;
-    const int n = inst / half, c = inst - n * half;
-    const int64_t base = ((int64_t)n * C + c) * HW;
-    ibn_fwd_row<LANES, U>(x + base, y + base, HW, t, red, true, 0.f, 0.f, in_eps, in_gamma ? in_gamma[c] : 1.f, in_beta ? in_beta[c] : 0.f,
-                          act, in_mean + inst, in_invstd + inst);
+__device__ __forceinline__ void ibn_bwd_row(const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ yact,
+                                            float* __restrict__ dx, int64_t row, int HW, int t, float* red, int kind, float mu, float is,
+                                            float a, float b, const float* __restrict__ gamma, int c, int act,
+                                            float* __restrict__ s1_out, float* __restrict__ s2_out) {
+    if constexpr (U > 0) ibn_row_bwd_reg<LANES, U>(x, dy, yact, dx, row, HW, t, red, kind, mu, is, a, b, gamma, c, act, s1_out, s2_out);
+    else norm_row_bwd<LANES, 0>(x, dy, yact, dx, nullptr, 0u, row, HW, t, red, kind, mu, is, a, b, gamma, c, act, 0.f, s1_out, s2_out, nullptr);
 }
 
 // every row of the tensor.  Row sums go to row_s1 / row_s2 [N][W]: W = half in train mode (IN rows only; the BN rows take the channel
@@ -1960,28 +1812,30 @@ __global__ __launch_bounds__(256) void ibn_bwd_rows_kernel(const float* __restri
     __shared__ float red[4];
     const int row = (int)blockIdx.x * (256 / LANES) + (int)threadIdx.x / LANES;
     if (row >= NC) return;
-    const int t = (int)threadIdx.x % LANES;
     const int n = row / C, c = row - n * C;
-    const int64_t base = (int64_t)row * HW;
-    const float* yp = act != RG_ACT_NONE ? yact + base : nullptr;
-    const int W = train ? half : C;
-    if (c < half) {
-        const int inst = n * half + c;
-        const float is = in_invstd[inst];
-        ibn_bwd_row<LANES, U>(x + base, dy + base, yp, dx + base, HW, t, red, IBN_ROW_IN, in_mean[inst], is,
-                              (in_gamma ? in_gamma[c] : 1.f) * is, 0.f, 0.f, act, row_s1 + n * W + c, row_s2 + n * W + c);
-    } else if (train) {
-        const int sc = c - half;
-        const float is = bn_stat[sc];
-        ibn_bwd_row<LANES, U>(x + base, dy + base, yp, dx + base, HW, t, red, IBN_ROW_BN_TRAIN, bn_mean[sc], is,
-                              (bn_gamma ? bn_gamma[sc] : 1.f) * is, bn_s1[sc] * inv_count, bn_s2[sc] * inv_count * is, act, nullptr,
-                              nullptr);
+    const bool in_row = c < half;
+    const int pc = in_row ? c : c - half;
+    const int kind = in_row ? IBN_ROW_IN : train ? IBN_ROW_BN_TRAIN : IBN_ROW_BN_EVAL;
+    const int so = n * (train ? half : C) + c;                   // the row's place in row_s1 / row_s2 (not for train-mode BN rows)
+    float mu, is, a = 0.f, b = 0.f;
+    if (in_row) {
+        mu = in_mean[n * half + c];
+        is = in_invstd[n * half + c];
     } else {
-        const int sc = c - half;
-        const float is = rsqrtf(bn_stat[sc] + bn_eps);
-        ibn_bwd_row<LANES, U>(x + base, dy + base, yp, dx + base, HW, t, red, IBN_ROW_BN_EVAL, bn_mean[sc], is,
-                              (bn_gamma ? bn_gamma[sc] : 1.f) * is, 0.f, 0.f, act, row_s1 + n * W + c, row_s2 + n * W + c);
+        mu = bn_mean[pc];
+        is = train ? bn_stat[pc] : rsqrtf(bn_stat[pc] + bn_eps);
+        if (train) {
+            a = bn_s1[pc] * inv_count;
+            b = bn_s2[pc] * inv_count * is;
+        }
     }
+    auto body = [&](int k) {                                     // one copy per kind: the register rows drop what a kind does not need
+        ibn_bwd_row<LANES, U>(x, dy, yact, dx, (int64_t)row * HW, HW, (int)threadIdx.x % LANES, red, k, mu, is, a, b,
+                              in_row ? in_gamma : bn_gamma, pc, act, row_s1 + so, row_s2 + so);
+    };
+    if (kind == IBN_ROW_IN) body(IBN_ROW_IN);
+    else if (kind == IBN_ROW_BN_TRAIN) body(IBN_ROW_BN_TRAIN);
+    else body(IBN_ROW_BN_EVAL);
 }
 
 template <int LANES, int U>
@@ -2002,38 +1856,18 @@ __global__ __launch_bounds__(256) void ibn_train_bwd_fused_kernel(const float* _
     }
     const int inst = ((int)blockIdx.x - cb) * (256 / LANES) + (int)threadIdx.x / LANES;
     if (inst >= N * half) return;
-    const int t = (int)threadIdx.x % LANES;
     const int n = inst / half, c = inst - n * half;
-    const int64_t base = ((int64_t)n * C + c) * HW;
-    const float is = in_invstd[inst];
-    ibn_bwd_row<LANES, U>(x + base, dy + base, act != RG_ACT_NONE ? yact + base : nullptr, dx + base, HW, t, red, IBN_ROW_IN,
-                          in_mean[inst], is, (in_gamma ? in_gamma[c] : 1.f) * is, 0.f, 0.f, act, row_s1 + inst, row_s2 + inst);
+    ibn_bwd_row<LANES, U>(x, dy, yact, dx, ((int64_t)n * C + c) * HW, HW, (int)threadIdx.x % LANES, red, IBN_ROW_IN, in_mean[inst],
+                          in_invstd[inst], 0.f, 0.f, in_gamma, c, act, row_s1 + inst, row_s2 + inst);
 }
 
 static bool ibn_train_fused(int N, int HW) { return (int64_t)N * HW <= 16384; }
 
-// float4 per lane of the register rows for this map (2 or 8), 0 = the loop rows
-static int ibn_reg_units(int HW) {
-    if (!g_bn_reg || (HW & 3)) return 0;
-    const int lanes = in_lanes(HW);
-    const int per = ((HW >> 2) + lanes - 1) / lanes;
-    return per <= 2 ? 2 : per <= 8 ? 8 : 0;
+// float4 per lane of the register rows for this tensor (2 or 8), 0 = the loop rows
+static int ibn_reg_units(int N, int C, int HW) {
+    const int units = row_reg_units(HW, in_lanes(HW), (int64_t)N * C * HW);
+    return units == 0 ? 0 : units <= 2 ? 2 : 8;
 }
-
-// lane-group dispatch of the four kernels above: ROWS lane groups after LEAD whole workgroups
-#define RG_IBN_CASE(KERNEL, L_, U_, LEAD, ROWS, ...)                                                                                    \
-    case L_ * 16 + U_:                                                                                                                 \
-        hipLaunchKernelGGL((KERNEL<L_, U_>), dim3((LEAD) + rg::cdiv(ROWS, 256 / L_)), dim3(256), 0, stream, __VA_ARGS__);                \
-        break
-#define RG_IBN_LAUNCH(KERNEL, LEAD, ROWS, ...)                                                                                          \
-    switch (in_lanes(HW) * 16 + ibn_reg_units(HW)) {                                                                                   \
-        RG_IBN_CASE(KERNEL, 16, 0, LEAD, ROWS, __VA_ARGS__); RG_IBN_CASE(KERNEL, 16, 2, LEAD, ROWS, __VA_ARGS__);                        \
-        RG_IBN_CASE(KERNEL, 32, 0, LEAD, ROWS, __VA_ARGS__); RG_IBN_CASE(KERNEL, 32, 2, LEAD, ROWS, __VA_ARGS__);                        \
-        RG_IBN_CASE(KERNEL, 64, 0, LEAD, ROWS, __VA_ARGS__); RG_IBN_CASE(KERNEL, 64, 2, LEAD, ROWS, __VA_ARGS__);                        \
-        RG_IBN_CASE(KERNEL, 64, 8, LEAD, ROWS, __VA_ARGS__);                                                                           \
-        RG_IBN_CASE(KERNEL, 256, 0, LEAD, ROWS, __VA_ARGS__); RG_IBN_CASE(KERNEL, 256, 8, LEAD, ROWS, __VA_ARGS__);                      \
-        default: rg::set_error("rg_ibn: no kernel for %d lanes x %d units", in_lanes(HW), ibn_reg_units(HW)); return RG_ERR_INVALID;    \
-    }
 
 // bytes of workspace for rg_ibn_fwd / rg_ibn_bwd: the slice partials of the BN half, then the row sums [2][N][C]
 extern "C" int64_t rg_ibn_workspace(int N, int C, int HW, int half) {
@@ -2055,30 +1889,36 @@ extern "C" int rg_ibn_fwd(const float* x, const float* in_gamma, const float* in
     RG_REQUIRE(train ? (bn_mean && bn_invstd) : (running_mean && running_var),
                train ? "rg_ibn_fwd: train mode writes the batch statistics" : "rg_ibn_fwd: eval mode needs the running statistics");
     const int NC = N * C, cb = C - half;
+    const bool fused = train && ibn_train_fused(N, HW);
     rg::ProfScope prof(rg::FAM_NORM, stream, 0.0, 8.0 * (double)NC * HW);
-    if (!train) {
-        RG_IBN_LAUNCH(ibn_fwd_rows_kernel, 0, NC, x, in_gamma, in_beta, bn_gamma, bn_beta, running_mean, running_var, y, in_mean,
-                      in_invstd, NC, C, half, HW, 1, in_eps, bn_eps, act);
-        return rg::check_launch("rg_ibn_fwd");
+    if (train && !fused) {
+        int L;
+        const int S = pick_slices(N, cb, HW, &L);
+        if (!workspace || workspace_bytes < (size_t)cb * S * 3 * sizeof(float)) {
+            rg::set_error("rg_ibn_fwd: workspace too small");
+            return RG_ERR_WORKSPACE;
+        }
+        float* part = static_cast<float*>(workspace);
+        // the BN half's statistics: the slice kernels over channels [half, C) — same sample stride C*HW, channel 0 of the view = half
+        hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(S, cb), dim3(256), 0, stream, x + (int64_t)half * HW, part, N, C, HW, L);
+        hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(rg::cdiv(cb, 64)), dim3(64), 0, stream, part, cb, S, bn_eps, momentum, bn_mean,
+                           bn_invstd, running_mean, running_var);
     }
-    if (ibn_train_fused(N, HW)) {
-        RG_IBN_LAUNCH(ibn_train_fwd_fused_kernel, cb, N * half, x, in_gamma, in_beta, bn_gamma, bn_beta, y, in_mean, in_invstd, bn_mean,
-                      bn_invstd, running_mean, running_var, N, C, half, HW, in_eps, bn_eps, momentum, act);
-        return rg::check_launch("rg_ibn_fwd");
+    const int lanes = in_lanes(HW), units = ibn_reg_units(N, C, HW);
+    const unsigned bytes = units ? (unsigned)((int64_t)NC * HW * 4) : 0u;
+    if (!with_lanes_units(IbnPairs{}, lanes, units, [&](auto L, auto U) {
+            if (fused)
+                hipLaunchKernelGGL((ibn_train_fwd_fused_kernel<L, U>), dim3(cb + rg::cdiv(N * half, 256 / L)), dim3(256), 0, stream, x,
+                                   in_gamma, in_beta, bn_gamma, bn_beta, y, in_mean, in_invstd, bn_mean, bn_invstd, running_mean,
+                                   running_var, N, C, half, HW, in_eps, bn_eps, momentum, act, bytes);
+            else
+                hipLaunchKernelGGL((ibn_fwd_rows_kernel<L, U>), dim3(rg::cdiv(NC, 256 / L)), dim3(256), 0, stream, x, in_gamma, in_beta,
+                                   bn_gamma, bn_beta, train ? bn_mean : running_mean, train ? bn_invstd : running_var, y, in_mean,
+                                   in_invstd, NC, C, half, HW, train ? 0 : 1, in_eps, bn_eps, act, bytes);
+        })) {
+        rg::set_error("rg_ibn_fwd: no kernel for %d lanes x %d units", lanes, units);
+        return RG_ERR_INVALID;
     }
-    int L;
-    const int S = pick_slices(N, cb, HW, &L);
-    if (!workspace || workspace_bytes < (size_t)cb * S * 3 * sizeof(float)) {
-        rg::set_error("rg_ibn_fwd: workspace too small");
-        return RG_ERR_WORKSPACE;
-    }
-    float* part = static_cast<float*>(workspace);
-    // the BN half's statistics: the slice kernels over channels [half, C) — same sample stride C*HW, channel 0 of the view = half
-    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(S, cb), dim3(256), 0, stream, x + (int64_t)half * HW, part, N, C, HW, L);
-    hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(rg::cdiv(cb, 64)), dim3(64), 0, stream, part, cb, S, bn_eps, momentum, bn_mean,
-                       bn_invstd, running_mean, running_var);
-    RG_IBN_LAUNCH(ibn_fwd_rows_kernel, 0, NC, x, in_gamma, in_beta, bn_gamma, bn_beta, bn_mean, bn_invstd, y, in_mean, in_invstd, NC, C,
-                  half, HW, 0, in_eps, bn_eps, act);
     return rg::check_launch("rg_ibn_fwd");
 }
 
@@ -2094,6 +1934,7 @@ extern "C" int rg_ibn_bwd(const float* x, const float* dy, const float* y_act, c
     RG_REQUIRE(act == RG_ACT_NONE || y_act, "rg_ibn_bwd: fused activation needs the forward output");
     RG_REQUIRE((int64_t)N * C < (1ll << 31) && (int64_t)N * HW < (1ll << 30), "rg_ibn_bwd: N*C or N*HW too large");
     const int NC = N * C, cb = C - half;
+    const bool fused = train && ibn_train_fused(N, HW);
     int L;
     const int S = pick_slices(N, cb, HW, &L);
     const size_t part_floats = (size_t)cb * S * 3;
@@ -2105,28 +1946,34 @@ extern "C" int rg_ibn_bwd(const float* x, const float* dy, const float* y_act, c
     float* row_s1 = part + part_floats;
     float* row_s2 = row_s1 + NC;
     rg::ProfScope prof(rg::FAM_NORM, stream, 0.0, (act ? 16.0 : 12.0) * (double)NC * HW);
-    if (!train) {
-        RG_IBN_LAUNCH(ibn_bwd_rows_kernel, 0, NC, x, dy, y_act, in_mean, in_invstd, in_gamma, bn_mean, bn_stat, bn_gamma, nullptr,
-                      nullptr, dx, row_s1, row_s2, NC, C, half, HW, 0, bn_eps, 0.f, act);
-        hipLaunchKernelGGL(rows_sum_pair_kernel, dim3(rg::cdiv(C, 16)), dim3(256), 0, stream, row_s1, row_s2, d_in_beta, d_in_gamma, N,
-                           C, half, d_bn_beta, d_bn_gamma);
-        return rg::check_launch("rg_ibn_bwd");
-    }
-    if (ibn_train_fused(N, HW)) {
-        RG_IBN_LAUNCH(ibn_train_bwd_fused_kernel, cb, N * half, x, dy, y_act, in_mean, in_invstd, in_gamma, bn_mean, bn_stat, bn_gamma,
-                      dx, row_s1, row_s2, d_bn_beta, d_bn_gamma, N, C, half, HW, act);
-    } else {
+    if (train && !fused) {                                       // the BN half's channel sums ARE d_bn_beta / d_bn_gamma
         const int64_t off = (int64_t)half * HW;
         hipLaunchKernelGGL(bn_bwd_reduce_partial_kernel, dim3(S, cb), dim3(256), 0, stream, x + off, dy + off,
                            y_act ? y_act + off : nullptr, bn_mean, bn_stat, part, N, C, HW, L, 0, bn_eps, act, 0.f);
         hipLaunchKernelGGL(bn_bwd_reduce_finalize_kernel, dim3(rg::cdiv(cb, 64)), dim3(64), 0, stream, part, cb, S, d_bn_beta,
                            d_bn_gamma);
-        RG_IBN_LAUNCH(ibn_bwd_rows_kernel, 0, NC, x, dy, y_act, in_mean, in_invstd, in_gamma, bn_mean, bn_stat, bn_gamma, d_bn_beta,
-                      d_bn_gamma, dx, row_s1, row_s2, NC, C, half, HW, 1, bn_eps, 1.f / (float)((int64_t)N * HW), act);
     }
-    hipLaunchKernelGGL(rows_sum_pair_kernel, dim3(rg::cdiv(half, 16)), dim3(256), 0, stream, row_s1, row_s2, d_in_beta, d_in_gamma, N,
-                       half, half, nullptr, nullptr);
+    const int lanes = in_lanes(HW), units = ibn_reg_units(N, C, HW);
+    if (!with_lanes_units(IbnPairs{}, lanes, units, [&](auto L_, auto U) {
+            if (fused)
+                hipLaunchKernelGGL((ibn_train_bwd_fused_kernel<L_, U>), dim3(cb + rg::cdiv(N * half, 256 / L_)), dim3(256), 0, stream, x,
+                                   dy, y_act, in_mean, in_invstd, in_gamma, bn_mean, bn_stat, bn_gamma, dx, row_s1, row_s2, d_bn_beta,
+                                   d_bn_gamma, N, C, half, HW, act);
+            else
+                hipLaunchKernelGGL((ibn_bwd_rows_kernel<L_, U>), dim3(rg::cdiv(NC, 256 / L_)), dim3(256), 0, stream, x, dy, y_act, in_mean,
+                                   in_invstd, in_gamma, bn_mean, bn_stat, bn_gamma, train ? d_bn_beta : nullptr,
+                                   train ? d_bn_gamma : nullptr, dx, row_s1, row_s2, NC, C, half, HW, train ? 1 : 0, bn_eps,
+                                   train ? 1.f / (float)((int64_t)N * HW) : 0.f, act);
+        })) {
+        rg::set_error("rg_ibn_bwd: no kernel for %d lanes x %d units", lanes, units);
+        return RG_ERR_INVALID;
+    }
+    // the row sums over n: the IN gradients in train mode (row sums [N][half]), all four in eval mode ([N][C], split at half)
+    if (train)
+        hipLaunchKernelGGL(rows_sum_pair_kernel, dim3(rg::cdiv(half, 16)), dim3(256), 0, stream, row_s1, row_s2, d_in_beta, d_in_gamma, N,
+                           half, half, nullptr, nullptr);
+    else
+        hipLaunchKernelGGL(rows_sum_pair_kernel, dim3(rg::cdiv(C, 16)), dim3(256), 0, stream, row_s1, row_s2, d_in_beta, d_in_gamma, N,
+                           C, half, d_bn_beta, d_bn_gamma);
     return rg::check_launch("rg_ibn_bwd");
 }
-#undef RG_IBN_LAUNCH
-#undef RG_IBN_CASE

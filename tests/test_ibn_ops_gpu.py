@@ -23,6 +23,13 @@ SHAPES = [
     (4, 128, 32, 16),    # HW 512
     (4, 256, 16, 8),     # HW 128, 128 BN channels
     (2, 2, 256, 128),    # HW 32 768: one workgroup per row
+    # register rows that do not fill their lanes (N*C leaves the last workgroup partly empty)
+    (3, 6, 4, 5),        # HW 20 = 5 float4: 16 lanes x 2 units, most lanes empty
+    (3, 6, 11, 12),      # HW 132 = 33 float4: 32 lanes x 2 units, the second unit on one lane
+    (3, 6, 13, 20),      # HW 260 = 65 float4: 64 lanes x 2 units, ragged
+    (3, 6, 12, 43),      # HW 516 = 129 float4: 64 lanes x 8 units, ragged
+    (2, 4, 27, 76),      # HW 2052 = 513 float4: 256 lanes x 8 units, ragged, one launch in train mode
+    (9, 4, 27, 76),      # the same rows with N*HW = 18 468: slice-parallel statistics, train-mode BN rows in the rows kernel
 ]
 EPS, MOM = 1e-5, 0.1
 
