@@ -217,7 +217,7 @@ __global__ __launch_bounds__(256) void softmax_ce_fwd_kernel(const float* __rest
     }
 }
 
-// dz[b][k] = g_b * scale * (softmax - onehot); g_b = grow[b] (per-row upstream) * gscale
+// dz[b][k] = g_b * scale * (softmax - onehot); g_b = grow[b] (per-row upstream) * gscale; 0 for a label outside [0, K)
 __global__ __launch_bounds__(256) void softmax_ce_bwd_kernel(const float* __restrict__ z, const int64_t* __restrict__ labels,
                                                              const float* __restrict__ lse,
                                                              const float* __restrict__ grow, float* __restrict__ dz,
@@ -228,6 +228,10 @@ __global__ __launch_bounds__(256) void softmax_ce_bwd_kernel(const float* __rest
     const float g = (grow ? grow[b] : 1.f) * gscale * scale;
     const float l = lse[b];
     const int64_t y = labels[b];
+    if (y < 0 || y >= K) {  // ignored row (the forward gave it loss 0): no gradient
+        for (int i = threadIdx.x; i < K; i += 256) dr[i] = 0.f;
+        return;
+    }
     for (int i = threadIdx.x; i < K; i += 256) {
         float p = expf(zr[i] * scale - l);
         if (i == y) p -= 1.f;
