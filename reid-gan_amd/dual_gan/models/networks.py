@@ -15,6 +15,7 @@ from rg_hip import nn as rnn
 from rg_hip import ops
 from rg_hip.ops import ACT_RELU, ACT_TANH
 from rg_hip.tape import RGModule
+from rg_hip.wcache import krsc_wanted
 from .base_function import (EncoderBlock, EncoderBlockOptimized, FeatureAdaptBlock1, Output, ResBlock, ResBlockDecoder,
                             ResBlockEncoder, ResBlockEncoderOptimized, SpectralNorm, get_nonlinearity_layer,
                             get_norm_layer, init_net, _slope)
@@ -669,7 +670,7 @@ class ResDiscriminator(RGModule):
             w = w_sn
         else:
             w, rec = conv.weight.detach(), None
-        wk = ops.weights_to_krsc(w) if (w.shape[2] * w.shape[3] > 1 and w.shape[1] % 4 == 0) else None
+        wk = ops.weights_to_krsc(w) if krsc_wanted(w.shape) else None
         return w, wk, rec
 
     def gp_forward(self, tape, x):

@@ -64,7 +64,7 @@ def parse_header(path=HEADER_PATH):
 
 
 def proto_hash(protos):
-    """sha1 over the canonical prototype list; must match csrc/gen_pymod.py:proto_hash (the generated module embeds it)"""
+    """sha1 over the canonical prototype list (the generated module embeds it: csrc/gen_pymod.py)"""
     import hashlib
     h = hashlib.sha1()
     for name, (ret, args) in protos.items():
@@ -83,7 +83,7 @@ def build(verbose=False):
     return LIB_PATH
 
 
-_PLAIN_INT = {"rg_version", "rg_family_count", "rg_fold_chunk", "rg_bn_slices", "rg_conv2d_dgrad_rowsum_cols", "rg_f8_grad_tiles", "rg_krsc_chunk", "rg_conv_set_planes", "rg_conv_tune_stats", "rg_conv_splitk_inkernel_count", "rg_conv_set_pick", "rg_conv_pick_log"}   # int-returning queries that are not status codes
+PLAIN_INT = {"rg_version", "rg_family_count", "rg_fold_chunk", "rg_bn_slices", "rg_conv2d_dgrad_rowsum_cols", "rg_f8_grad_tiles", "rg_krsc_chunk", "rg_conv_set_planes", "rg_conv_tune_stats", "rg_conv_splitk_inkernel_count", "rg_conv_set_pick", "rg_conv_pick_log"}   # int-returning queries that are not status codes
 
 
 class _Lib(object):
@@ -153,7 +153,7 @@ class _Lib(object):
                 return fn
             raw = getattr(self._dll, name)
             ret = self.protos[name][0]
-            if ret != "int" or name in _PLAIN_INT:
+            if ret != "int" or name in PLAIN_INT:
                 return raw
             dll = self._dll
 

@@ -21,6 +21,7 @@ import torch
 from . import ops
 from .lib import lib
 from .ops import _chk, _p, _pair, _stream, workspace
+from .wcache import Stamp
 
 E4M3, E5M2 = 0, 1
 FMAX = (448.0, 57344.0)
@@ -192,7 +193,7 @@ class F8Layer(object):
         self.sx = states.new(E4M3)          # input activations
         self.sw = states.new(E4M3)          # filters
         self.sdy = states.new(E5M2)         # output gradients
-        self._wkey = None
+        self._wstamp = Stamp()
         self._wq = None
 
     def quant_act(self, x, layout):
@@ -220,13 +221,14 @@ class F8Layer(object):
 
     def weights(self, w, key=None):
         """(wq [K][RS][Cp], wq_t [C][RS][Kp]) of the filter tensor, re-quantised (always with a fresh amax: filters are
-        small) when `key` changes; key=None: every call (spectral-normed filters change every forward)."""
-        if key is None or key != self._wkey or ops.CAPTURING[0]:
+        small) when `key` changes (wcache.Stamp: and on every call while a network program is captured); key=None: every call
+        (spectral-normed filters change every forward)."""
+        if key is None or self._wstamp.stale(key):
             # filters change by one optimizer step between uses: the previous step's maximum scales them (delayed policy);
             # 'jit' measures first
             self.sw.prepare(w)
             self._wq = quantize_dual(w, self.sw, True, True)
-            self._wkey = None if ops.CAPTURING[0] else key      # recorded, not executed, inside a capture: stays stale for eager code
+            self._wstamp.set(key)
         return self._wq
 
 

@@ -14,7 +14,7 @@ training flag, input shapes and requires_grad pattern, whether parameter gradien
 contribution of the step.  What a replay does NOT re-run is the Python of the programs, so its host-side effects are either forced to
 be unconditional during capture (filter re-layout / fp8 re-quantisation caches refresh every time: `ops.CAPTURING`), re-applied per
 replay (BatchNorm `num_batches_tracked` bookkeeping), or a reason not to graph the network (active Dropout draws a seed from the host
-generator per call; an active launch profiler needs the eager launches).
+generator per call; an active launch profiler needs the eager launches; a BatchNorm fold is refused by the fold itself, nn._fold_of).
 
 Memory: a record's inputs are copied into static buffers, its intermediates / outputs / saved activations live in the record's private
 graph pool (torch.cuda.graph), exactly as they would stay resident for the backward in eager mode; a network called k times before
@@ -27,7 +27,7 @@ import os
 import torch
 
 from . import ops
-from .tape import Tape
+from .tape import Tape, run_backward
 
 ENABLED = os.environ.get("RG_NET_GRAPHS", "1") != "0"
 WARMUP = 2          # eager calls per key before capture (first-use calibration of fp8 scales, lazily built caches)
@@ -109,7 +109,7 @@ def _capture_forward(net, xs, params):
                 outs = net.tf(rec.tape, *rec.static_in)
     except Exception:
         # the aborted program's Python side effects must not survive it: none of its kernels ran.  Cache keys are not stamped while
-        # capturing (nn._KrscCache / KrscGroup / lowp.F8Layer); the BatchNorm step counters are put back here.
+        # capturing (wcache.Stamp); the BatchNorm step counters are put back here.
         for b, n0 in zip(bns, before):
             b.__dict__["_nbt_pending"] = n0
         raise
@@ -130,35 +130,6 @@ def _replay_forward(rec, xs):
     rec.fwd.replay()
     for b, d in rec.bn_deltas:
         b.__dict__["_nbt_pending"] = b.__dict__.get("_nbt_pending", 0) + d
-
-
-def _tb_and_grads(net, tape, dys, need, params):
-    """the body of tape._NetFn.backward: run the backward program and settle the parameter gradients (arena views are assigned,
-    everything else is returned); -> (dxs, grads per parameter, [(param, arena view)] assignments made)"""
-    ops.side_begin()                  # no-op unless RG_GRAPH_SIDE keeps the weight-gradient side stream inside the capture
-    try:
-        dxs = net.tb(tape, *dys, need_dx=any(need))
-    finally:
-        ops.side_join()               # fork / join nodes of the graph: weight gradients are complete from here on
-    if not isinstance(dxs, (tuple, list)):
-        dxs = (dxs,)
-    dxs = tuple(dxs) + (None,) * (len(need) - len(dxs))
-    grads, assign = [], []
-    for p in params:
-        g = tape.grads.get(id(p))
-        v = getattr(p, "_rg_grad", None)
-        if g is None or v is None:
-            grads.append(g)
-        elif g.data_ptr() == v.data_ptr():
-            p.grad = v
-            assign.append((p, v))
-            grads.append(None)
-        elif p.grad is not None and p.grad.data_ptr() == v.data_ptr():
-            ops.axpby(v, g, 1.0, 1.0, out=v)
-            grads.append(None)
-        else:
-            grads.append(g)
-    return dxs, grads, assign
 
 
 def _grad_pattern(params):
@@ -205,7 +176,7 @@ class _GraphedFn(torch.autograd.Function):
                 try:
                     with _capture_mode():
                         with torch.cuda.graph(g, pool=rec.pool, capture_error_mode=_CAPTURE_MODE):
-                            dxs, grads, assign = _tb_and_grads(net, rec.tape, rec.static_dys, need, params)
+                            dxs, grads, assign = run_backward(net, rec.tape, rec.static_dys, need, params)
                 except Exception as e:
                     # a backward program that cannot be captured: run THIS backward eagerly over the record's tape (the forward
                     # replay produced its saved activations for real) and retire the record; the key runs eagerly from now on
@@ -219,7 +190,7 @@ class _GraphedFn(torch.autograd.Function):
                             ent["bad"] = True
                     rec.tape.stack[:] = stack0
                     rec.tape.grads = {}
-                    dxs, grads, assign = _tb_and_grads(net, rec.tape, list(dys), need, params)
+                    dxs, grads, assign = run_backward(net, rec.tape, list(dys), need, params)
                     rec.tape = None
                     hook = getattr(net, "_rg_after_backward", None)
                     if hook is not None and params:

@@ -16,16 +16,11 @@ from torch.nn import init
 from . import ops
 from .ops import ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_TANH
 from .tape import RGModule
+from .wcache import GroupStamp, Stamp, krsc_wanted, weight_key
 
 
 def _pair(v):
     return (v, v) if isinstance(v, int) else (int(v[0]), int(v[1]))
-
-
-import weakref
-
-WEIGHT_EPOCH = [0]      # bumped by rg_hip.optim after every step (its kernels bypass torch's version counters)
-BN_LAYERS = weakref.WeakSet()      # rg_hip.graph advances their host-side `num_batches_tracked` bookkeeping per replay
 
 
 def _geom_gflop(geom, dy):
@@ -76,44 +71,40 @@ def sn_prepare(convs, training):
 
 
 class _KrscCache(object):
-    """[K][KH*KW][C] copy of a filter tensor for the (r,s)-major kernels, rebuilt only when the weights changed.  Convolutions of one
-    network share a KrscGroup (group_krsc): the first stale member re-lays ALL of them out in one launch."""
-
-    def _krsc_wanted(self):
-        w = self.weight
-        return not (w.shape[2] * w.shape[3] == 1 or w.shape[1] % 4 != 0)
-
-    def _krsc_key(self):
-        w = self.weight
-        arena = getattr(w, "_rg_arena", None)          # the fused optimizers bump their own arena's epoch
-        return (arena.epoch if arena is not None else WEIGHT_EPOCH[0], w._version, w.data_ptr())
+    """[K][KH*KW][C] copy of a filter tensor for the (r,s)-major kernels, rebuilt only when the weights changed (wcache.Stamp).
+    Convolutions of one network share a KrscGroup (group_krsc): the first stale member re-lays ALL of them out in one launch."""
 
     def _krsc(self):
-        if not self._krsc_wanted():
+        w = self.weight
+        if not krsc_wanted(w.shape):
             return None
-        grp = self.__dict__.get("_krsc_group")
+        d = self.__dict__
+        grp = d.get("_krsc_group")
         if grp is not None:
             return grp.get(self)
-        key = self._krsc_key()
-        if getattr(self, "_wk_key", None) != key or ops.CAPTURING[0]:
-            self._wk = ops.weights_to_krsc(self.weight.detach())
-            # inside a capture nothing executes (and the copy lives in the capture's pool): the key stays stale, so eager code that
-            # runs after the capture — including the fallback of a capture that FAILED — rebuilds the copy for real
-            self._wk_key = None if ops.CAPTURING[0] else key
+        stamp = d.get("_wk_stamp")
+        if stamp is None:
+            stamp = d["_wk_stamp"] = Stamp()
+        key = weight_key(w)
+        if stamp.stale(key):
+            self._wk = ops.weights_to_krsc(w.detach())
+            stamp.set(key)
         return self._wk
 
 
 class KrscGroup(object):
     """The (r,s)-major filter copies of every plain convolution of one network, refreshed together by ONE launch
-    (`rg_weights_to_krsc_multi`) when the first member finds its copy stale — after an optimizer step every member is.  The copies
-    are persistent buffers; the device table is rebuilt when a parameter moved (load_state_dict, .to())."""
+    (`rg_weights_to_krsc_multi`) when the first member finds its copy stale — after an optimizer step every member is
+    (wcache.GroupStamp).  The copies are persistent buffers; the device table is rebuilt when a parameter moved (load_state_dict,
+    .to())."""
 
     def __init__(self, candidates):
         self.members = []                 # the candidates that actually asked for their copy (folded convolutions never do)
+        self.stamps = []                  # their `_wk_stamp`
+        self.stamp = GroupStamp()
         self.ptrs = None
         self.table = None
         self.blocks = 0
-        self.cap_gen = -1
         for m in candidates:
             m.__dict__["_krsc_group"] = self
 
@@ -139,21 +130,19 @@ class KrscGroup(object):
                 raise RuntimeError("KrscGroup: a parameter moved while a network program is being captured")
             self._build()
         ops.lib.rg_weights_to_krsc_multi(ops._p(self.table), len(self.members), self.blocks, ops._stream())
-        for m in self.members:           # (recorded, not executed, inside a capture: keys stay stale there — see _KrscCache._krsc)
-            m._wk_key = None if ops.CAPTURING[0] else m._krsc_key()
+        self.stamp.set(self.stamps, [weight_key(m.weight) for m in self.members])
 
     def get(self, m):
-        if not m.__dict__.get("_krsc_member"):
+        d = m.__dict__
+        if not d.get("_krsc_member"):
             if ops.CAPTURING[0]:
                 raise RuntimeError("KrscGroup: a convolution asked for its (r,s)-major filters for the first time inside a capture")
-            m.__dict__["_krsc_member"] = True
+            d["_krsc_member"] = True
+            d["_wk_stamp"] = Stamp()      # stale: the refresh below rebuilds the table with the new member in it
             self.members.append(m)
-            self.ptrs = None              # table rebuilt by the refresh below (the new member's key is stale)
-        if ops.CAPTURING[0]:
-            if self.cap_gen != ops.CAPTURE_GEN[0]:       # once per captured program: the refresh is one of its nodes
-                self.refresh()
-                self.cap_gen = ops.CAPTURE_GEN[0]
-        elif m.__dict__.get("_wk_key") != m._krsc_key():
+            self.stamps.append(d["_wk_stamp"])
+            self.ptrs = None
+        if self.stamp.stale(d["_wk_stamp"], weight_key(m.weight)):
             self.refresh()
         return m._wk
 
@@ -172,7 +161,7 @@ def group_krsc(net):
     if not isinstance(root, nn.Module):
         return
     members = [m for m in root.modules() if isinstance(m, _KrscCache) and isinstance(getattr(m, "weight", None), torch.Tensor)
-               and m.weight.is_cuda and m._krsc_wanted() and "_krsc_group" not in m.__dict__]
+               and m.weight.is_cuda and krsc_wanted(m.weight.shape) and "_krsc_group" not in m.__dict__]
     if len(members) >= 2:
         KrscGroup(members)
 
@@ -201,11 +190,6 @@ class Conv2d(RGModule, _KrscCache):
         return (x.shape[0], x.shape[1], x.shape[2], x.shape[3], self.weight.shape[0], self.kernel_size[0], self.kernel_size[1],
                 self.stride[0], self.stride[1], self.padding[0], self.padding[1])
 
-    def _wkey(self):
-        w = self.weight
-        arena = getattr(w, "_rg_arena", None)
-        return (arena.epoch if arena is not None else WEIGHT_EPOCH[0], w._version, w.data_ptr())
-
     def tf(self, tape, x, act=ACT_NONE, slope=0.0, residual=None):
         """y = act(conv(x) + bias + residual): bias, residual add and activation run in the MFMA epilogue."""
         f8 = self.__dict__.get("_rg_f8")
@@ -214,7 +198,7 @@ class Conv2d(RGModule, _KrscCache):
             from . import lowp
             want_w = tape.record and tape.wants(self.weight)
             xq, xq_t = f8.quant_act_both(x, want_w)
-            wq, _ = f8.weights(self.weight.detach(), self._wkey())
+            wq, _ = f8.weights(self.weight.detach(), weight_key(self.weight))
             geom = self._geom(x)
             y = lowp.conv_fwd(xq, wq, geom, shift=self.bias, residual=residual, act=act, slope=slope)
             tape.push((xq_t, y if act != ACT_NONE else None, act, slope, geom))
@@ -253,7 +237,7 @@ class Conv2d(RGModule, _KrscCache):
                                                            worth=ops.side_worth(_geom_gflop(geom, dy), fp8=True)))
             if not need_dx:
                 return None
-            _, wq_t = f8.weights(self.weight.detach(), self._wkey())
+            _, wq_t = f8.weights(self.weight.detach(), weight_key(self.weight))
             return lowp.conv_dgrad(dyq, wq_t, geom, (geom[2], geom[3]), residual=residual)
         x, y, act, slope = tape.pop()
         if act != ACT_NONE:
@@ -304,11 +288,6 @@ class ConvTranspose2d(RGModule, _KrscCache):
         return (self.out_channels, hw[0], hw[1], self.in_channels, self.kernel_size[0], self.kernel_size[1], self.stride[0],
                 self.stride[1], self.padding[0], self.padding[1])
 
-    def _wkey(self):
-        w = self.weight
-        arena = getattr(w, "_rg_arena", None)
-        return (arena.epoch if arena is not None else WEIGHT_EPOCH[0], w._version, w.data_ptr())
-
     def tf(self, tape, x, act=ACT_NONE, slope=0.0, residual=None):
         hw = self.out_hw(x.shape[2], x.shape[3])
         f8 = self.__dict__.get("_rg_f8")
@@ -317,7 +296,7 @@ class ConvTranspose2d(RGModule, _KrscCache):
             from . import lowp
             want_w = tape.record and tape.wants(self.weight)
             xq, xq_t = f8.quant_act_both(x, want_w)
-            _, wq_t = f8.weights(self.weight.detach(), self._wkey())
+            _, wq_t = f8.weights(self.weight.detach(), weight_key(self.weight))
             geom = (x.shape[0],) + self._geom(hw)
             y = lowp.conv_dgrad(xq, wq_t, geom, hw, shift=self.bias, residual=residual, act=act, slope=slope)
             tape.push((xq_t, y if act != ACT_NONE else None, act, slope, geom))
@@ -350,7 +329,7 @@ class ConvTranspose2d(RGModule, _KrscCache):
                                                            worth=ops.side_worth(_geom_gflop(geom, dy), fp8=True)))
             if not need_dx:
                 return None
-            wq, _ = f8.weights(self.weight.detach(), self._wkey())
+            wq, _ = f8.weights(self.weight.detach(), weight_key(self.weight))
             return lowp.conv_fwd(dyq, wq, geom, residual=residual)
         x, y, act, slope = tape.pop()
         if act != ACT_NONE:
@@ -400,7 +379,6 @@ class Linear(RGModule):
 class _BatchNorm(RGModule):
     def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True, track_running_stats=True):
         super(_BatchNorm, self).__init__()
-        BN_LAYERS.add(self)
         self.num_features, self.eps, self.momentum = num_features, eps, momentum
         self.affine, self.track_running_stats = affine, track_running_stats
         if affine:
@@ -523,24 +501,29 @@ def _foldable(conv, bn):
             and isinstance(conv, Conv2d))
 
 
-def _pair_key(conv, bn):
-    w, g = conv.weight, bn.weight
-    aw, ag = getattr(w, "_rg_arena", None), getattr(g, "_rg_arena", None)
-    return (aw.epoch if aw is not None else WEIGHT_EPOCH[0], ag.epoch if ag is not None else WEIGHT_EPOCH[0],
-            w._version, g._version, bn.bias._version, bn.running_mean._version, bn.running_var._version, w.data_ptr(),
-            g.data_ptr())
+_FOLD_IN_CAPTURE = ("a network that folds BatchNorm into its convolutions cannot be captured: a replay would keep the filters "
+                    "scaled at capture time after every later optimizer step")
+
+
+def _fold_key(conv, bn):
+    """weight_key of the five tensors a fold is made from (read from the modules' own dicts: nn.Module.__getattr__ per tensor would
+    cost several times the key, and conv_bn_tf asks on every call)"""
+    p, b = bn._parameters, bn._buffers
+    return weight_key(conv._parameters["weight"], p["weight"], p["bias"], b["running_mean"], b["running_var"])
 
 
 def _fold_of(conv, bn):
     """Per-pair fold (one small launch group); networks fold all their pairs at once through FoldGroup."""
-    key = _pair_key(conv, bn)
+    if ops.CAPTURING[0]:
+        raise RuntimeError(_FOLD_IN_CAPTURE)
+    key = _fold_key(conv, bn)
     f = getattr(conv, "_rg_fold", None)
     if f is None or f.key != key:
         f = _Fold()
         f.key = key
         f.scale, f.shift, f.invstd = ops.bn_fold(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps)
         ws = f.w_scaled = ops.scale_rows(conv.weight.detach(), f.scale)
-        f.w_scaled_krsc = ops.weights_to_krsc(ws) if (ws.shape[2] * ws.shape[3] > 1 and ws.shape[1] % 4 == 0) else None
+        f.w_scaled_krsc = ops.weights_to_krsc(ws) if krsc_wanted(ws.shape) else None
         conv._rg_fold = f
     return f
 
@@ -551,8 +534,8 @@ class FoldGroup(object):
 
     def __init__(self, pairs):
         self.pairs = list(pairs)
-        self.key = None
-        self.table = None
+        self.keys = None                  # per pair: _fold_key its fold in `folds` was made for
+        self.ptrs = None                  # per pair: the five input addresses `table` holds
 
     def _build(self, device):
         chunk = lib_fold_chunk()
@@ -560,7 +543,7 @@ class FoldGroup(object):
         for conv, bn in self.pairs:
             w = conv.weight
             n_w += (w.numel() + 63) // 64 * 64
-            if w.shape[2] * w.shape[3] > 1 and w.shape[1] % 4 == 0:
+            if krsc_wanted(w.shape):
                 n_k += (w.numel() + 63) // 64 * 64
             n_c += (w.shape[0] + 63) // 64 * 64
         self.buf_w = torch.empty(n_w + n_k, dtype=torch.float32, device=device)
@@ -573,7 +556,7 @@ class FoldGroup(object):
             f = _Fold()
             f.w_scaled = self.buf_w[ow:ow + w.numel()].view(w.shape)
             ow += (w.numel() + 63) // 64 * 64
-            if RS > 1 and C % 4 == 0:
+            if krsc_wanted(w.shape):
                 f.w_scaled_krsc = self.buf_w[ow:ow + w.numel()].view(K, RS, C)
                 ow += (w.numel() + 63) // 64 * 64
             else:
@@ -591,27 +574,25 @@ class FoldGroup(object):
             self.folds.append(f)
         self.table = torch.tensor(rows, dtype=torch.int64).to(device)
         self.blocks = blocks
-        self.ptrs = self._ptrs()
-
-    def _ptrs(self):
-        return tuple(conv.weight.data_ptr() for conv, _ in self.pairs) + tuple(bn.weight.data_ptr() for _, bn in self.pairs)
 
     def usable(self):
         return all(_foldable(conv, bn) for conv, bn in self.pairs)
 
     def prepare(self):
-        """Fold every pair if any weight changed since the last call; afterwards conv._rg_fold is current."""
-        conv0, bn0 = self.pairs[0]
-        ptrs = self._ptrs()
-        if self.table is None or ptrs != self.ptrs:
-            self._build(conv0.weight.device)
-        key = tuple(_pair_key(conv, bn)[:7] for conv, bn in self.pairs)
-        if key == self.key:
+        """Fold every pair if any weight changed or moved since the last call; afterwards conv._rg_fold is current."""
+        if ops.CAPTURING[0]:
+            raise RuntimeError(_FOLD_IN_CAPTURE)
+        keys = [_fold_key(conv, bn) for conv, bn in self.pairs]
+        if keys == self.keys:
             return
+        ptrs = [[p for _, _, p in key] for key in keys]
+        if ptrs != self.ptrs:
+            self._build(self.pairs[0][0].weight.device)
+            self.ptrs = ptrs
         ops.fold_filters_multi(self.table, len(self.pairs), self.blocks)
-        self.key = key
-        for (conv, bn), f in zip(self.pairs, self.folds):
-            f.key = _pair_key(conv, bn)
+        self.keys = keys
+        for (conv, _), f, key in zip(self.pairs, self.folds, keys):
+            f.key = key
             conv._rg_fold = f
 
 
@@ -983,7 +964,7 @@ class SNConv2d(RGModule):
             y = lowp.conv_fwd(xq, wq, geom, shift=self.bias, residual=residual, act=act, slope=slope)
             tape.push((xq_t, y if act != ACT_NONE else None, act, slope, w_sn, (wq_t, geom), sigma, u, v))
             return y
-        wk = ops.weights_to_krsc(w_sn) if (w_sn.shape[2] * w_sn.shape[3] > 1 and w_sn.shape[1] % 4 == 0) else None
+        wk = ops.weights_to_krsc(w_sn) if krsc_wanted(w_sn.shape) else None
         y = ops.conv2d_fwd(x, w_sn, self.stride, self.padding, shift=self.bias, residual=residual, act=act, slope=slope,
                            w_krsc=wk)
         tape.push((x, y if act != ACT_NONE else None, act, slope, w_sn, wk, sigma, u, v))

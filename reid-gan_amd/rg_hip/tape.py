@@ -61,6 +61,36 @@ class Tape(object):
             self.grads[k] = ops.axpby(prev, g, 1.0, 1.0, out=prev)
 
 
+def run_backward(net, tape, dys, need, params):
+    """Run the backward program of `net` and settle the parameter gradients: a gradient written straight into the optimizer's
+    arena is assigned to `.grad`, a later contribution is accumulated into it, everything else is handed to autograd.
+    -> (dxs padded to len(need), gradient per parameter for autograd (None when settled here), [(param, arena view)] assigned)"""
+    ops.side_begin()                  # (inside a capture: a no-op unless RG_GRAPH_SIDE keeps the weight-gradient side stream on)
+    try:
+        dxs = net.tb(tape, *dys, need_dx=any(need))
+    finally:
+        ops.side_join()               # weight gradients launched on the side stream are complete from here on
+    if not isinstance(dxs, (tuple, list)):
+        dxs = (dxs,)
+    dxs = tuple(dxs) + (None,) * (len(need) - len(dxs))
+    grads, assign = [], []
+    for p in params:
+        g = tape.grads.get(id(p))
+        v = getattr(p, "_rg_grad", None)
+        if g is None or v is None:
+            grads.append(g)
+        elif g.data_ptr() == v.data_ptr():                    # written straight into the gradient arena
+            p.grad = v
+            assign.append((p, v))
+            grads.append(None)
+        elif p.grad is not None and p.grad.data_ptr() == v.data_ptr():
+            ops.axpby(v, g, 1.0, 1.0, out=v)                  # accumulate across backward calls
+            grads.append(None)
+        else:
+            grads.append(g)
+    return dxs, grads, assign
+
+
 class _NetFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, net, n_in, *tensors):
@@ -78,28 +108,7 @@ class _NetFn(torch.autograd.Function):
         if tape is None:
             raise RuntimeError("rg_hip: backward through a network a second time (the tape is freed after backward)")
         need = ctx.needs_input_grad[2:2 + n_in]
-        ops.side_begin()
-        try:
-            dxs = ctx.net.tb(tape, *dys, need_dx=any(need))
-        finally:
-            ops.side_join()          # weight gradients launched on the side stream are complete from here on
-        if not isinstance(dxs, (tuple, list)):
-            dxs = (dxs,)
-        dxs = tuple(dxs) + (None,) * (n_in - len(dxs))
-        grads = []
-        for p in ctx.params:
-            g = tape.grads.get(id(p))
-            v = getattr(p, "_rg_grad", None)
-            if g is None or v is None:
-                grads.append(g)
-            elif g.data_ptr() == v.data_ptr():                    # written straight into the gradient arena
-                p.grad = v
-                grads.append(None)
-            elif p.grad is not None and p.grad.data_ptr() == v.data_ptr():
-                ops.axpby(v, g, 1.0, 1.0, out=v)                  # accumulate across backward calls
-                grads.append(None)
-            else:
-                grads.append(g)
+        dxs, grads, _ = run_backward(ctx.net, tape, dys, need, ctx.params)
         ctx.tape = None
         hook = getattr(ctx.net, "_rg_after_backward", None)
         if hook is not None and grads:      # e.g. start this network's gradient all-reduce while upstream runs

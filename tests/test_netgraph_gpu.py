@@ -172,6 +172,66 @@ def test_uncapturable_network_falls_back_to_eager_with_fresh_caches(dev):
     assert int(ng.bn.num_batches_tracked) == int(ne.bn.num_batches_tracked)
 
 
+def test_folding_network_refuses_capture_and_runs_eagerly(dev):
+    """A network that folds frozen BatchNorm into its convolutions must not be captured: a program recorded while the fold was
+    fresh would hold no fold launch and replay the filters scaled at capture time after every later optimizer step.  FoldGroup.prepare
+    and the per-pair fold raise inside a capture, so the network stays eager, loudly — same numbers as a twin that never tries."""
+    import warnings
+    from rg_hip import nn as rnn, netgraph as NG
+    from rg_hip.tape import RGModule
+
+    class Net(RGModule):
+        def __init__(self):
+            super(Net, self).__init__()
+            self.c1 = rnn.Conv2d(16, 16, 3, 1, 1, bias=False)
+            self.b1 = rnn.BatchNorm2d(16)
+            self.c2 = rnn.Conv2d(16, 8, 3, 1, 1, bias=False)
+            self.b2 = rnn.BatchNorm2d(8)
+            self.folds = rnn.FoldGroup([(self.c1, self.b1), (self.c2, self.b2)])
+
+        def tf(self, tape, x):
+            assert self.folds.usable()
+            self.folds.prepare()
+            h = rnn.conv_bn_tf(tape, self.c1, self.b1, x, act=rnn.ACT_RELU)
+            return rnn.conv_bn_tf(tape, self.c2, self.b2, h)
+
+        def tb(self, tape, dy, need_dx=True):
+            d = rnn.conv_bn_tb(tape, self.c2, self.b2, dy)
+            return rnn.conv_bn_tb(tape, self.c1, self.b1, d, need_dx=need_dx)
+
+    torch.manual_seed(7)
+    ng, ne = Net().to(dev).eval(), Net().to(dev).eval()
+    with torch.no_grad():
+        for bn in (ng.b1, ng.b2):                         # statistics and an affine map that make the fold more than a copy
+            bn.running_mean.normal_(0.0, 0.2)
+            bn.running_var.uniform_(0.5, 1.5)
+            bn.weight.uniform_(0.5, 1.5)
+            bn.bias.normal_(0.0, 0.2)
+    ne.load_state_dict(ng.state_dict())
+    ng.__dict__["_rg_graph"] = True
+    og, oe = torch.optim.SGD(ng.parameters(), lr=0.01), torch.optim.SGD(ne.parameters(), lr=0.01)
+    with warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter("always")
+        for it in range(NG.WARMUP + 3):
+            gen = torch.Generator(device=dev).manual_seed(90 + it)
+            x, x2 = (torch.randn(4, 16, 16, 8, device=dev, generator=gen) for _ in range(2))
+            outs = []
+            for net, opt in ((ng, og), (ne, oe)):
+                opt.zero_grad()
+                y1, y2 = net(x), net(x2)                  # two forwards in flight before the backward
+                (y1.pow(2).mean() + 2.0 * y2.pow(2).mean()).backward()
+                opt.step()
+                outs.append((y1.detach(), y2.detach()))
+            for a, b in zip(outs[0], outs[1]):
+                assert torch.isfinite(b).all() and torch.equal(a, b), it
+            for a, b in zip(ng.parameters(), ne.parameters()):
+                assert torch.equal(a, b), it
+    assert any("not capturable" in str(w.message) and "cannot be captured" in str(w.message) for w in caught)
+    st = NG.stats(ng)
+    assert st and all(rec == 0 and not ok for _, rec, ok in st.values()), st
+    assert all(p.grad is not None and bool(p.grad.abs().sum() > 0) for p in ne.parameters())
+
+
 def test_uncapturable_backward_falls_back_to_eager(dev):
     """forward program captured, backward program not capturable (host read-back in tb): that backward runs eagerly over the record's
     tape, the record is retired and the key stays eager — same numbers as a twin that never captures"""
