@@ -136,7 +136,7 @@ __global__ __launch_bounds__(256) void l2norm_rows_fwd_kernel(const float* __res
     if (norm && threadIdx.x == 0) norm[blockIdx.x] = nr;
 }
 
-// dx = (dy - y * <dy, y>) / max(norm, eps)   (for norm > eps; for norm <= eps: dy / eps)
+// dx = (dy - y * <dy, y>) / max(norm, eps)   (for norm >= eps, where clamp_min passes the gradient; for norm < eps: dy / eps)
 __global__ __launch_bounds__(256) void l2norm_rows_bwd_kernel(const float* __restrict__ y, const float* __restrict__ dy,
                                                               const float* __restrict__ norm, float* __restrict__ dx,
                                                               int D, float eps) {
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(256) void l2norm_rows_bwd_kernel(const float* __res
     s = rg_block_sum(s, red);
     const float nr = norm[blockIdx.x];
     const float inv = 1.f / fmaxf(nr, eps);
-    const float k = nr > eps ? s : 0.f;
+    const float k = nr >= eps ? s : 0.f;
     for (int i = threadIdx.x; i < D; i += blockDim.x) dr[i] = (gr[i] - yr[i] * k) * inv;
 }
 
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(256) void l2norm_channels_bwd_kernel(const float* _
     for (int i = 0; i < G; ++i) dot += red[i][lp];
     const float nr = norm[(int64_t)n * HW + px];
     const float inv = 1.f / fmaxf(nr, eps);
-    const float k = nr > eps ? dot : 0.f;
+    const float k = nr >= eps ? dot : 0.f;
 #pragma unroll 8
     for (int c = g; c < C; c += G) dx[base + (int64_t)c * HW] = (dy[base + (int64_t)c * HW] - y[base + (int64_t)c * HW] * k) * inv;
 }

@@ -130,8 +130,8 @@ __device__ __forceinline__ void p_store(prsrc_t r, unsigned off, float v) {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), r, off, 0, 0);
 }
 __device__ __forceinline__ float pad_act(float v, int act, float slope) {          // uniform act: selects
-    const float neg = act == RG_ACT_LEAKY ? slope : 0.f;
-    return act == RG_ACT_NONE ? v : (v > 0.f ? v : v * neg);
+    // selects as rg_apply_act: ReLU of a negative value is +0.0 (v * 0 would be -0.0, and NaN for -inf)
+    return act == RG_ACT_NONE ? v : (v > 0.f ? v : (act == RG_ACT_LEAKY ? v * slope : 0.f));
 }
 __device__ __forceinline__ float pad_act_grad(float xv, int act, float slope) {
     const float neg = act == RG_ACT_LEAKY ? slope : 0.f;

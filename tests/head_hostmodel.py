@@ -147,9 +147,11 @@ def exact(v):
     return Ref(v, torch.zeros_like(v), "exact")
 
 
-def compare(got, ref):
+def compare(got, ref, table=None):
     """per-element check of `got` against ref = Ref(value, M, kind); every element takes part.  An element whose reference is
-    NaN or infinite passes only with the same NaN / infinity; a non-finite `got` anywhere else fails."""
+    NaN or infinite passes only with the same NaN / infinity; a non-finite `got` anywhere else fails.  table: the constants
+    per kind (default C_KIND; another host model brings its own kinds)"""
+    table = C_KIND if table is None else table
     g = got.detach().double().cpu().reshape(-1)
     v, M = ref.value.reshape(-1), ref.M.reshape(-1)
     assert g.numel() == v.numel(), ("shape", tuple(got.shape), tuple(ref.value.shape))
@@ -158,7 +160,7 @@ def compare(got, ref):
     err = torch.where(torch.isfinite(err), err, torch.full_like(err, float("inf")))
     if ref.kind != "exact":
         M = M + TINY_M
-    bud = C_KIND[ref.kind] * U24 * M
+    bud = table[ref.kind] * U24 * M
     over = err - bud
     i = int(torch.argmax(over)) if over.numel() else 0
     ratio = torch.where(err > 0, err / (U24 * M).clamp_min(1e-300), torch.zeros_like(err))
