@@ -499,6 +499,40 @@ int rg_global_avgpool_bwd(const float* dy, float* dx, int N, int C, int HW, rg_s
 int rg_gem_pool_fwd(const float* x, const float* p, float* y, int N, int C, int HW, float eps, rg_stream_t stream);
 int rg_gem_pool_bwd(const float* x, const float* p, const float* y, const float* dy, float* dx, float* dp, int N,
                     int C, int HW, float eps, void* workspace, size_t workspace_bytes, rg_stream_t stream);
+/* part pooling of the multi-part encoder, CC/clustercontrast/models/resnet_mp.py:111-114: y / dy are [2][N][C]; part 0 pools
+   rows [0, split_row) of every plane, part 1 rows [split_row, H) (0 < split_row < H), both read in one pass.  p NULL: average
+   pooling, else GeM with the one-element device exponent.  bwd writes every element of dx once; GeM reads x and the forward's y,
+   dp (1 element, may be NULL) is the exponent gradient of both parts, summed through workspace (N*C floats) in a fixed order;
+   average pooling reads neither x nor y and takes dp NULL */
+int rg_part_pool_fwd(const float* x, const float* p, float* y, int N, int C, int H, int W, int split_row, float eps,
+                     rg_stream_t stream);
+int rg_part_pool_bwd(const float* x, const float* p, const float* y, const float* dy, float* dx, float* dp, int N, int C,
+                     int H, int W, int split_row, float eps, void* workspace, size_t workspace_bytes, rg_stream_t stream);
+
+/* ---- fused [B][D] tail of the multi-part encoder, CC/clustercontrast/models/resnet_mp.py:118-143 ---------------------------
+ * z_j = BatchNorm1d_j(x_j) for the three branches j = g, p1, p2 (each with its own gamma, beta, running statistics, momentum and
+ * eps; train: biased batch statistics, running statistics updated with the unbiased variance; eval: running statistics),
+ * z_gc = z_g + z_p1 + z_p2 (fusion 1) or z_g (fusion 0), out[k] = z_k / max(|z_k|, 1e-12) per row for k = g, p1, p2, gc.
+ *   forward   out [4][B][D]; saved for the backward: xhat [3][B][D] (the normalised activations), mean / invstd [3][D] (the batch
+ *             statistics, or the running mean and rsqrt(running_var + eps) in eval mode), norms [4][B].  Train: 2 launches and
+ *             rg_mp_head_workspace bytes of workspace (B >= 2); eval: 1 launch, no workspace.
+ *   backward  any of the four upstream gradients may be NULL (an unused output); dz_j (may be NULL) is a gradient arriving at z_j
+ *             itself (the 'cat' fusion reads the BatchNorm outputs).  dx_j / dgamma_j / dbeta_j may be NULL; dx_j only
+ *             when no given gradient reaches branch j (then the branch is skipped), a branch without dx takes no affine
+ *             gradients.  dx_j doubles as scratch between the two launches.
+ * Deterministic (fixed summation order, no atomics). */
+int64_t rg_mp_head_workspace(int B, int D);
+int rg_mp_head_fwd(const float* x_g, const float* x_p1, const float* x_p2, const float* gamma_g, const float* gamma_p1,
+                   const float* gamma_p2, const float* beta_g, const float* beta_p1, const float* beta_p2, float* rm_g,
+                   float* rm_p1, float* rm_p2, float* rv_g, float* rv_p1, float* rv_p2, float* out, float* xhat, float* mean,
+                   float* invstd, float* norms, int B, int D, int train, int fusion, float eps_g, float eps_p1, float eps_p2,
+                   float mom_g, float mom_p1, float mom_p2, void* workspace, size_t workspace_bytes, rg_stream_t stream);
+int rg_mp_head_bwd(const float* dy_g, const float* dy_p1, const float* dy_p2, const float* dy_gc, const float* dz_g,
+                   const float* dz_p1, const float* dz_p2, const float* xhat, const float* invstd, const float* norms,
+                   const float* gamma_g, const float* gamma_p1, const float* gamma_p2, const float* beta_g,
+                   const float* beta_p1, const float* beta_p2, float* dx_g, float* dx_p1, float* dx_p2,
+                   float* dgamma_g, float* dgamma_p1, float* dgamma_p2, float* dbeta_g, float* dbeta_p1, float* dbeta_p2, int B,
+                   int D, int train, int fusion, rg_stream_t stream);
 
 /* ---- losses (scalar outputs live in device memory; grad_out is a 1-element device tensor or NULL) */
 size_t rg_loss_workspace(void);

@@ -56,6 +56,20 @@ class _ReducerCache(object):
         return r
 
 
+def intra_cl(q, k, temperature, group_size=16):
+    """group contrast of trainers.py:200-210: logits[n, g] = sum over the g-th group of k of <q_n, k_m> / T."""
+    from clustercontrast.models.cm import _MatmulT
+    q = RF.normalize_rows(q)
+    k = RF.normalize_rows(k)
+    logits = _MatmulT.apply(q, k)
+    qs, ks = logits.shape
+    ones = torch.zeros(ks // group_size, ks, device=q.device)
+    ones[torch.arange(ks, device=q.device) // group_size, torch.arange(ks, device=q.device)] = 1.0
+    grouped = _MatmulT.apply(logits, ones)                         # sums each group of `group_size` keys
+    targets = torch.arange(group_size, dtype=torch.long, device=q.device).repeat_interleave(group_size)
+    return RF.cross_entropy_rows(grouped, targets, 1.0 / temperature)
+
+
 class ClusterContrastTrainer(object):
     def __init__(self, encoder, memory=None):
         super(ClusterContrastTrainer, self).__init__()
@@ -117,6 +131,40 @@ class ClusterContrastTrainer(object):
 
     def _forward(self, inputs):
         return self.encoder(inputs)
+
+
+class ClusterContrastPartTrainer(ClusterContrastTrainer):
+    """The reference's multi-part recipe (trainers.py:79-93) without its GAN term, for the `resnet_mp50` encoder, whose train-mode
+    forward returns (f_g, f_p1, f_p2, f_gc):
+
+        loss = memory(f_gc, labels).mean() + intra_cl(f_p1, f_p1.detach()).mean() + intra_cl(f_p2, f_p2.detach()).mean()
+               + intra_cl(f_g, f_g.detach()).mean()
+
+    `group_size` (instances per identity in a batch; the batch size is group_size^2 in the reference's sampler) and `temperature`
+    (its `opt.cl_temp`) are constructor arguments.
+
+    Data-parallel reduction: the encoder has two branches behind `base` and its `base` is not a whole trunk, so
+    rg_hip.parallel.attach_stage_hooks finds no trunk in it and no stage hook is placed; every parameter that received a gradient —
+    `base`, `res_g`, `res_p`, the pooling exponent and the three head BatchNorm weights — is reduced exactly once by the
+    end-of-backward `reduce()` of `step`."""
+
+    def __init__(self, encoder, memory=None, group_size=16, temperature=0.05):
+        super(ClusterContrastPartTrainer, self).__init__(encoder, memory)
+        self.group_size = group_size
+        self.T = temperature
+
+    def step(self, inputs, labels, optimizer):
+        reducer = self._reducers.get(optimizer, self.encoder)     # replicas are synchronised (rank-0 broadcast) BEFORE the first forward
+        f_g, f_p1, f_p2, f_gc = self._forward(inputs)
+        terms = [RF.weighted_mean(self.memory(f_gc, labels))]
+        for f in (f_p1, f_p2, f_g):
+            terms.append(RF.weighted_mean(intra_cl(f, f.detach(), self.T, self.group_size)))
+        loss = RF._WeightedSum.apply(torch.stack(terms), None, 1.0)
+        optimizer.zero_grad()
+        _backward(loss)
+        reducer.reduce()
+        optimizer.step()
+        return loss.detach()
 
 
 class ClusterContrastWithGANTrainer(object):
@@ -243,17 +291,8 @@ class ClusterContrastWithGANTrainer(object):
         return self.encoder(inputs, fuse=fuse)
 
     def intra_cl(self, q, k, group_size=16):
-        """group contrast of trainers.py:200-210: logits[n, g] = sum over the g-th group of k of <q_n, k_m> / T."""
-        from clustercontrast.models.cm import _MatmulT
-        q = RF.normalize_rows(q)
-        k = RF.normalize_rows(k)
-        logits = _MatmulT.apply(q, k)
-        qs, ks = logits.shape
-        ones = torch.zeros(ks // group_size, ks, device=q.device)
-        ones[torch.arange(ks, device=q.device) // group_size, torch.arange(ks, device=q.device)] = 1.0
-        grouped = _MatmulT.apply(logits, ones)                         # sums each group of `group_size` keys
-        targets = torch.arange(group_size, dtype=torch.long, device=q.device).repeat_interleave(group_size)
-        return RF.cross_entropy_rows(grouped, targets, 1.0 / self.T)
+        """group contrast of trainers.py:200-210 at this trainer's temperature (the module-level `intra_cl`)."""
+        return intra_cl(q, k, self.T, group_size)
 
 
 class GANTrainer(object):

@@ -190,6 +190,105 @@ __global__ __launch_bounds__(256) void gem_bwd_kernel(const float* __restrict__ 
     }
 }
 
+// Part pooling of the multi-part encoder (CC/clustercontrast/models/resnet_mp.py:111-114): the rows [0, split_row) and
+// [split_row, H) of an NCHW plane are the contiguous element ranges [0, n0) and [n0, HW), so one wave reads the plane once and
+// produces both pooled values; the backward writes every element of the dx plane once.  One wave per plane like the kernels
+// above.  A plane base is 16-byte aligned only when HW % 4 == 0 and n0 need not be a multiple of 4: `head` scalar elements lead
+// up to the first aligned address, float4 units follow (a unit that straddles n0 sends each element to its own part), the
+// last HW - head & 3 elements are scalar again.
+__device__ __forceinline__ int part_pool_head(const void* plane_base, int HW) {
+    const int head = (int)((4u - ((unsigned)(reinterpret_cast<uintptr_t>(plane_base) >> 2) & 3u)) & 3u);
+    return head < HW ? head : HW;
+}
+
+template <bool GEM>
+__global__ __launch_bounds__(256) void part_pool_fwd_kernel(const float* __restrict__ x, const float* __restrict__ pp,
+                                                            float* __restrict__ y, int planes, int HW, int n0, float eps) {
+    const int plane = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (plane >= planes) return;
+    const int lane = threadIdx.x & 63;
+    const float p = GEM ? pp[0] : 1.f;
+    const float* xp = x + (int64_t)plane * HW;
+    float s0 = 0.f, s1 = 0.f;
+    auto take = [&](float v, int i) {
+        const float t = GEM ? exp2f(p * log2f(fmaxf(v, eps))) : v;               // xc^p, xc >= eps > 0
+        if (i < n0) s0 += t; else s1 += t;
+    };
+    const int head = part_pool_head(xp, HW);
+    if (lane < head) take(xp[lane], lane);
+    const int nv = (HW - head) >> 2;
+    for (int u = lane; u < nv; u += 64) {
+        const int i = head + 4 * u;
+        const float4 v = *reinterpret_cast<const float4*>(xp + i);
+        take(v.x, i), take(v.y, i + 1), take(v.z, i + 2), take(v.w, i + 3);
+    }
+    for (int i = head + 4 * nv + lane; i < HW; i += 64) take(xp[i], i);
+    s0 = rg_wave_sum(s0);
+    s1 = rg_wave_sum(s1);
+    if (lane < 2) {                                                              // lane 0 finishes part 0, lane 1 part 1: one powf deep
+        const float m = lane ? s1 / (float)(HW - n0) : s0 / (float)n0;
+        y[(int64_t)lane * planes + plane] = GEM ? powf(m, 1.f / p) : m;
+    }
+}
+
+// per part the formulas of gap_bwd_kernel / gem_bwd_kernel with the part's own element count; dp_part[plane] = part 0 + part 1
+template <bool GEM>
+__global__ __launch_bounds__(256) void part_pool_bwd_kernel(const float* __restrict__ x, const float* __restrict__ pp,
+                                                            const float* __restrict__ y, const float* __restrict__ dy,
+                                                            float* __restrict__ dx, float* __restrict__ dp_part, int planes,
+                                                            int HW, int n0, float eps) {
+    const int plane = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (plane >= planes) return;
+    const int lane = threadIdx.x & 63;
+    const float p = GEM ? pp[0] : 1.f;
+    const float cnt0 = (float)n0, cnt1 = (float)(HW - n0);
+    const float g0 = dy[plane], g1 = dy[(int64_t)planes + plane];
+    float y0 = 0.f, y1 = 0.f, m0 = 1.f, m1 = 1.f, c0, c1;
+    if (GEM) {
+        y0 = y[plane], y1 = y[(int64_t)planes + plane];
+        const float m = powf((lane & 1) ? y1 : y0, p);                          // mean(xc^p) of the part: both parts in one powf
+        m0 = __shfl(m, 0, 64), m1 = __shfl(m, 1, 64);
+        c0 = g0 * y0 / (m0 * cnt0), c1 = g1 * y1 / (m1 * cnt1);                 // g * m^(1/p-1) / count
+    } else {
+        c0 = g0 * (1.f / cnt0), c1 = g1 * (1.f / cnt1);
+    }
+    const float* xp = GEM ? x + (int64_t)plane * HW : nullptr;
+    float* dxp = dx + (int64_t)plane * HW;
+    float sl0 = 0.f, sl1 = 0.f;
+    auto grad = [&](float xv, int i) -> float {
+        if (!GEM) return i < n0 ? c0 : c1;
+        const float xc = fmaxf(xv, eps);
+        const float l2 = log2f(xc);
+        const float xpw = exp2f((p - 1.f) * l2);                                // xc^(p-1)
+        const float t = xpw * xc * (l2 * 0.6931471805599453f);
+        if (i < n0) sl0 += t; else sl1 += t;
+        return xv >= eps ? (i < n0 ? c0 : c1) * xpw : 0.f;
+    };
+    // float4 units only where x and dx planes share their offset from a 16-byte boundary
+    const bool vec = !GEM || ((reinterpret_cast<uintptr_t>(xp) ^ reinterpret_cast<uintptr_t>(dxp)) & 15) == 0;
+    const int head = vec ? part_pool_head(dxp, HW) : HW;
+    for (int i = lane; i < head; i += 64) dxp[i] = grad(GEM ? xp[i] : 0.f, i);
+    const int nv = (HW - head) >> 2;
+    for (int u = lane; u < nv; u += 64) {
+        const int i = head + 4 * u;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (GEM) v = *reinterpret_cast<const float4*>(xp + i);
+        float4 d;
+        d.x = grad(v.x, i), d.y = grad(v.y, i + 1), d.z = grad(v.z, i + 2), d.w = grad(v.w, i + 3);
+        *reinterpret_cast<float4*>(dxp + i) = d;
+    }
+    for (int i = head + 4 * nv + lane; i < HW; i += 64) dxp[i] = grad(GEM ? xp[i] : 0.f, i);
+    if (GEM && dp_part) {
+        sl0 = rg_wave_sum(sl0);
+        sl1 = rg_wave_sum(sl1);
+        const bool hi = lane & 1;                                               // even lanes evaluate part 0, odd lanes part 1
+        const float g = hi ? g1 : g0, yv = hi ? y1 : y0, m = hi ? m1 : m0;
+        const float d = g * yv * (-logf(m) / (p * p) + ((hi ? sl1 : sl0) / (hi ? cnt1 : cnt0)) / (p * m));
+        const float d1 = __shfl(d, 1, 64);
+        if (lane == 0) dp_part[plane] = d + d1;
+    }
+}
+
 __global__ __launch_bounds__(1024) void sum_all_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t n) {
     __shared__ float red[16];
     float s = 0.f;
@@ -284,4 +383,51 @@ extern "C" int rg_gem_pool_bwd(const float* x, const float* p, const float* y, c
                        eps);
     if (dp) hipLaunchKernelGGL(sum_all_kernel, dim3(1), dim3(1024), 0, stream, part, dp, (int64_t)planes);
     return rg::check_launch("rg_gem_pool_bwd");
+}
+
+// y: [2][N][C]; part 0 = rows [0, split_row), part 1 = rows [split_row, H) of every plane.  p == NULL: average pooling, else GeM
+// with the one-element device exponent.
+extern "C" int rg_part_pool_fwd(const float* x, const float* p, float* y, int N, int C, int H, int W, int split_row, float eps,
+                                hipStream_t stream) {
+    RG_REQUIRE(x && y && N > 0 && C > 0 && H > 0 && W > 0, "rg_part_pool_fwd: bad arguments");
+    RG_REQUIRE(split_row > 0 && split_row < H, "rg_part_pool_fwd: split row %d leaves a part of the %d rows empty", split_row, H);
+    RG_REQUIRE((int64_t)N * C <= (1 << 30) && (int64_t)H * W <= (1 << 30), "rg_part_pool_fwd: extents too large");
+    const int planes = N * C, HW = H * W, n0 = split_row * W;
+    rg::ProfScope prof(rg::FAM_POOL, stream, 0.0, 4.0 * planes * (double)HW);
+    if (p)
+        hipLaunchKernelGGL(part_pool_fwd_kernel<true>, dim3(rg::cdiv(planes, 4)), dim3(256), 0, stream, x, p, y, planes, HW, n0, eps);
+    else
+        hipLaunchKernelGGL(part_pool_fwd_kernel<false>, dim3(rg::cdiv(planes, 4)), dim3(256), 0, stream, x, p, y, planes, HW, n0,
+                           eps);
+    return rg::check_launch("rg_part_pool_fwd");
+}
+
+// dy: [2][N][C]; every element of dx is written once.  GeM (p given) reads x and the forward's y, and with dp (1 element) sums the
+// exponent gradient of both parts and all planes through workspace (N*C floats) in a fixed order; average pooling (p NULL)
+// reads neither x nor y, and dp must be NULL.
+extern "C" int rg_part_pool_bwd(const float* x, const float* p, const float* y, const float* dy, float* dx, float* dp, int N,
+                                int C, int H, int W, int split_row, float eps, void* workspace, size_t workspace_bytes,
+                                hipStream_t stream) {
+    RG_REQUIRE(dy && dx && N > 0 && C > 0 && H > 0 && W > 0, "rg_part_pool_bwd: bad arguments");
+    RG_REQUIRE(p ? (x && y) : !dp, "rg_part_pool_bwd: GeM needs x and y, average pooling has no exponent gradient");
+    RG_REQUIRE(split_row > 0 && split_row < H, "rg_part_pool_bwd: split row %d leaves a part of the %d rows empty", split_row, H);
+    RG_REQUIRE((int64_t)N * C <= (1 << 30) && (int64_t)H * W <= (1 << 30), "rg_part_pool_bwd: extents too large");
+    const int planes = N * C, HW = H * W, n0 = split_row * W;
+    float* part = nullptr;
+    if (dp) {
+        if (!workspace || workspace_bytes < (size_t)planes * sizeof(float)) {
+            rg::set_error("rg_part_pool_bwd: workspace too small");
+            return RG_ERR_WORKSPACE;
+        }
+        part = static_cast<float*>(workspace);
+    }
+    rg::ProfScope prof(rg::FAM_POOL, stream, 0.0, (p ? 8.0 : 4.0) * planes * (double)HW);
+    if (p)
+        hipLaunchKernelGGL(part_pool_bwd_kernel<true>, dim3(rg::cdiv(planes, 4)), dim3(256), 0, stream, x, p, y, dy, dx, part,
+                           planes, HW, n0, eps);
+    else
+        hipLaunchKernelGGL(part_pool_bwd_kernel<false>, dim3(rg::cdiv(planes, 4)), dim3(256), 0, stream, x, p, y, dy, dx, part,
+                           planes, HW, n0, eps);
+    if (dp) hipLaunchKernelGGL(sum_all_kernel, dim3(1), dim3(1024), 0, stream, part, dp, (int64_t)planes);
+    return rg::check_launch("rg_part_pool_bwd");
 }

@@ -184,8 +184,9 @@ def trunk_tf(tape, mods, x):
     return x
 
 
-def trunk_tb(tape, mods, dy, need_dx=True):
-    """Backward program of the trunk.  `mods[0]._rg_stage_hook(tape, params)` — set by rg_hip.parallel.attach_stage_hooks — is called
+def trunk_tb(tape, mods, dy, need_dx=True, dy_masked=False):
+    """Backward program of the trunk (dy_masked: dy already carries the ReLU backward of the last block's output — the consumers'
+    data-gradient epilogues applied it, as between two blocks).  `mods[0]._rg_stage_hook(tape, params)` — set by rg_hip.parallel.attach_stage_hooks — is called
     as each stage (layer4 .. layer1, then the stem) has launched its last weight gradient: the data-parallel all-reduce of that
     stage's range of the gradient arena starts there and runs under the backward of the stages below (the arena keeps a stage's
     parameters adjacent, so a stage is one element range)."""
@@ -199,7 +200,7 @@ def trunk_tb(tape, mods, dy, need_dx=True):
             i -= 1
             # every block's input except the first one's (the max-pool output) is the previous block's ReLU output: its
             # backward runs in this block's conv1 dgrad epilogue, so the block below receives an already masked gradient
-            dy = blk.tb(tape, dy, dy_masked=(i != nblk - 1), mask_input=(i != 0))
+            dy = blk.tb(tape, dy, dy_masked=(dy_masked or i != nblk - 1), mask_input=(i != 0))
         if hook is not None:
             hook(tape, [p for blk in layers[li] for p in blk.parameters()])
     dy = maxpool.tb(tape, dy)

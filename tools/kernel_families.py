@@ -38,12 +38,16 @@ FAMILY = {
     "bn_stats_from_partials_kernel": "norm", "bn_bwd_from_partials_kernel": "norm",
     "ibn_fwd_rows_kernel": "norm", "ibn_train_fwd_fused_kernel": "norm", "ibn_bwd_rows_kernel": "norm",
     "ibn_train_bwd_fused_kernel": "norm",
+    # part_head.hip
+    "mp_head_col_fwd_kernel": "norm", "mp_head_row_fwd_kernel": "norm", "mp_head_eval_fwd_kernel": "norm",
+    "mp_head_row_bwd_kernel": "norm", "mp_head_col_bwd_kernel": "norm",
     # optim.hip
     "adam_advance_kernel": "optim", "adam_dev_kernel": "optim", "adam_kernel": "optim", "sgd_kernel": "optim",
     "u64_add_kernel": "optim",
     # pool.hip
     "gap_bwd_kernel": "pool", "gap_fwd_kernel": "pool", "gem_bwd_kernel": "pool", "gem_fwd_kernel": "pool",
     "maxpool_bwd_3x3s2_kernel": "pool", "maxpool_bwd_kernel": "pool", "maxpool_fwd_kernel": "pool", "sum_all_kernel": "pool",
+    "part_pool_fwd_kernel": "pool", "part_pool_bwd_kernel": "pool",
     # eltwise.hip
     "act_bwd_kernel": "eltwise", "act_fwd_kernel": "eltwise", "axpby_kernel": "eltwise", "copy_channels_kernel": "eltwise",
     "dropout_kernel": "eltwise", "fill_kernel": "eltwise", "spin_kernel": "eltwise", "l2norm_rows_bwd_kernel": "eltwise",
