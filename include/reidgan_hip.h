@@ -197,6 +197,29 @@ int rg_ibn_bwd(const float* x, const float* dy, const float* y_act, const float*
                const float* bn_mean, const float* bn_stat, const float* in_gamma, const float* bn_gamma, float* dx,
                float* d_in_gamma, float* d_in_beta, float* d_bn_gamma, float* d_bn_beta, int N, int C, int HW, int half, int train,
                float bn_eps, int act, void* workspace, size_t workspace_bytes, rg_stream_t stream);
+/* Domain-specific BatchNorm (CC/clustercontrast/models/dsbn.py:6-42), train mode, on x[N][C][HW] with N even: samples [0, N/2) are
+ * normalised with their own batch statistics and the S parameter set, samples [N/2, N) with theirs and the T set — on the ONE
+ * tensor, no slice copies and no concatenation.  Everything rg_bn_train_*_fused offers is kept per domain: residual add, activation
+ * epilogue, running-statistics update (biased variance normalises, unbiased goes into running_var, count N/2*HW; any of the four
+ * running tensors may be NULL), y_act-masked backward, dx / dres either NULL; the channel sums are written straight into the four
+ * gradient outputs.  mean / invstd are [2][C] (S row, T row).
+ * Launches: (N/2)*HW <= 16384 (rg_dsbn_one_launch), whatever C: one per direction, 2C workgroups; otherwise three per direction
+ * as ONE BatchNorm — slice partial, finalize, apply over both domains, rg_dsbn_slices slices per domain, cut inside a domain and
+ * never across sample N/2.  Deterministic (fixed summation order, no atomics).  An odd N is refused before anything is launched.
+ * Eval mode is BatchNorm with the T set on the whole batch: use the rg_bn_* entry points.  workspace: rg_dsbn_workspace bytes. */
+int64_t rg_dsbn_workspace(int N, int C, int HW);
+int rg_dsbn_one_launch(int N, int C, int HW);
+int rg_dsbn_slices(int N, int C, int HW);
+/* float4 units per thread of the one-workgroup-per-channel train kernels for N samples (rg_bn_train_*_fused; rg_dsbn_* with N / 2):
+ * 1, 2, 4, 8, 16 = register kernels, 0 = loop kernels (scalar rows, more than 16 units per thread, or RG_BN_REG=0). */
+int rg_bn_reg_units(int N, int C, int HW);
+int rg_dsbn_fwd(const float* x, const float* gamma_s, const float* beta_s, const float* gamma_t, const float* beta_t,
+                const float* residual, float* y, float* mean, float* invstd, float* running_mean_s, float* running_var_s,
+                float* running_mean_t, float* running_var_t, int N, int C, int HW, float eps_s, float eps_t, float momentum_s,
+                float momentum_t, int act, float slope, void* workspace, size_t workspace_bytes, rg_stream_t stream);
+int rg_dsbn_bwd(const float* x, const float* dy, const float* y_act, const float* mean, const float* invstd, const float* gamma_s,
+                const float* gamma_t, float* dx, float* dres, float* d_gamma_s, float* d_beta_s, float* d_gamma_t, float* d_beta_t,
+                int N, int C, int HW, int act, float slope, void* workspace, size_t workspace_bytes, rg_stream_t stream);
 int rg_bn_bwd_apply(const float* x, const float* dy, const float* y_act, const float* mean, const float* stat,
                     const float* gamma, const float* sum_dy, const float* sum_dy_xhat, float* dx, float* dres, int N,
                     int C, int HW, int train, int stat_is_var, float eps, int act, float slope, rg_stream_t stream);

@@ -1,6 +1,8 @@
 """Model registry — mirrors CC/clustercontrast/models/__init__.py:6-59 for the ResNet family, the IBN-a ResNets (the
 encoder of the reference's published cluster-contrast recipe) and the multi-part encoder `resnet_mp50` (the one its flagship script
-builds); the two-branch (bip / bipd) and dsbn variants registered there are outside the hot path, SURVEY §2 row 20."""
+builds); the two-branch (bip / bipd) variants registered there are outside the hot path, SURVEY §2 row 20.  Domain-specific
+BatchNorm is no registered model but a conversion of one: `clustercontrast.models.dsbn` (convert_dsbn / convert_bn, as
+examples/test.py --dsbn uses them) on the fused two-domain layer rg_hip.nn.DSBN2d / DSBN1d."""
 from __future__ import absolute_import
 
 from rg_hip.overlay import extend as _rg_extend  # noqa: E402

@@ -19,6 +19,34 @@ struct WStat {
     float n, mean, m2;
 };
 
+// ---- domain-specific BatchNorm (DSBN) on the BatchNorm kernels ---------------------------------------------------------------------
+// A DSBN batch is [source half | target half] (h = N / 2 samples each) and every half has its own parameters and running statistics
+// (CC/clustercontrast/models/dsbn.py:6-23).  The halves of an [N][C][HW] tensor are contiguous, so (domain, channel) are 2C virtual
+// channels over h samples and a domain is a BatchNorm on a (sample base, sample count) view.  Every train-mode BatchNorm kernel below
+// therefore ends in a parameter pack `DS... ds`: empty for a BatchNorm (the kernel is then exactly what it was), one of the structs
+// here for the two-domain layer — the kernel is launched with h for N and one more grid plane, and its first lines move the
+// tensors to sample d * h, the statistics to row d of [2][C] and pick parameter set d.  There is one copy of every kernel body.
+struct DsbnSet {
+    const float* gamma;
+    const float* beta;
+    float* running_mean;
+    float* running_var;
+    float eps, momentum;
+};
+struct DsbnFwd {                      // forward kernels that read parameters or update running statistics
+    DsbnSet s[2];
+};
+struct DsbnBwd {                      // backward kernels
+    const float* gamma[2];
+    float* d_gamma[2];                // receive sum g * xhat
+    float* d_beta[2];                 // receive sum g
+};
+struct DsbnPlane {};                  // kernels that only need the domain's offset
+template <class T>
+__device__ __forceinline__ const T& dsbn_arg(const T& t) {
+    return t;
+}
+
 __device__ __forceinline__ WStat chan_merge(WStat a, WStat b) {
     WStat r;
     r.n = a.n + b.n;
@@ -47,8 +75,14 @@ __device__ __forceinline__ WStat wave_merge(WStat s) {
 }
 
 // grid (S, C): block (s, c) reduces elements [s*L, (s+1)*L) of channel c's N*HW values.
+template <class... DS>
 __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const float* __restrict__ x, float* __restrict__ part,
-                                                               int N, int C, int HW, int L) {
+                                                               int N, int C, int HW, int L, DS... ds) {
+    if constexpr (sizeof...(DS) > 0) {                 // the two-domain layer: this plane's half, statistics row and parameter set
+        const int d = blockIdx.z;
+        x += (int64_t)d * N * C * HW;
+        part += (int64_t)d * C * gridDim.x * 3;
+    }
     const int c = blockIdx.y, s = blockIdx.x, S = gridDim.x;
     const int64_t total = (int64_t)N * HW;
     const int64_t beg = (int64_t)s * L;
@@ -104,9 +138,18 @@ __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const float* __re
     }
 }
 
+template <class... DS>
 __global__ void bn_stats_finalize_kernel(const float* __restrict__ part, int C, int S, float eps, float momentum,
                                          float* __restrict__ mean, float* __restrict__ invstd,
-                                         float* __restrict__ running_mean, float* __restrict__ running_var) {
+                                         float* __restrict__ running_mean, float* __restrict__ running_var, DS... ds) {
+    if constexpr (sizeof...(DS) > 0) {                 // the two-domain layer: this plane's half, statistics row and parameter set
+        const int d = blockIdx.y;
+        const auto& a = dsbn_arg(ds...);
+        const DsbnSet p = d ? a.s[1] : a.s[0];
+        part += (int64_t)d * C * S * 3;
+        mean += d * C, invstd += d * C;
+        running_mean = p.running_mean, running_var = p.running_var, eps = p.eps, momentum = p.momentum;
+    }
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     WStat t;
@@ -133,12 +176,22 @@ __global__ void bn_stats_finalize_kernel(const float* __restrict__ part, int C, 
 
 // y = act((x - mean[c]) * invstd[c] * gamma[c] + beta[c] + res)
 // stat_is_var: `invstd` holds a variance (eval mode: running_var) and eps is applied here.
+template <class... DS>
 __global__ __launch_bounds__(256) void bn_apply_fwd_kernel(const float* __restrict__ x, const float* __restrict__ mean,
                                                            const float* __restrict__ invstd,
                                                            const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, const float* __restrict__ res,
                                                            float* __restrict__ y, int64_t total, int C, int HW,
-                                                           int stat_is_var, float eps, int act, float slope) {
+                                                           int stat_is_var, float eps, int act, float slope, DS... ds) {
+    if constexpr (sizeof...(DS) > 0) {                 // the two-domain layer: this plane's half, statistics row and parameter set
+        const int d = blockIdx.y;
+        const auto& a = dsbn_arg(ds...);
+        const DsbnSet p = d ? a.s[1] : a.s[0];
+        const int64_t o = d * total;
+        x += o, y += o, mean += d * C, invstd += d * C;
+        if (res) res += o;
+        gamma = p.gamma, beta = p.beta;
+    }
     if ((HW & 3) == 0) {
         const int64_t nv = total >> 2;
         for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
@@ -190,6 +243,7 @@ __device__ __forceinline__ float act_grad_from_out(float yv, int act, float slop
 }
 
 // partial sums over a slice: sum(dy_eff), sum(dy_eff * xhat); dy_eff = dy * act'(y)
+template <class... DS>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_partial_kernel(const float* __restrict__ x,
                                                                     const float* __restrict__ dy,
                                                                     const float* __restrict__ yact,
@@ -197,7 +251,14 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_partial_kernel(const float*
                                                                     const float* __restrict__ invstd,
                                                                     float* __restrict__ part, int N, int C, int HW,
                                                                     int L, int stat_is_var, float eps, int act,
-                                                                    float slope) {
+                                                                    float slope, DS... ds) {
+    if constexpr (sizeof...(DS) > 0) {                 // the two-domain layer: this plane's half, statistics row and parameter set
+        const int d = blockIdx.z;
+        const int64_t o = (int64_t)d * N * C * HW;
+        x += o, dy += o, mean += d * C, invstd += d * C;
+        if (yact) yact += o;
+        part += (int64_t)d * C * gridDim.x * 2;
+    }
     const int c = blockIdx.y, s = blockIdx.x, S = gridDim.x;
     const int64_t total = (int64_t)N * HW;
     const int64_t beg = (int64_t)s * L;
@@ -315,8 +376,15 @@ __global__ __launch_bounds__(256) void bn_eval_bwd_fused_kernel(const float* __r
     }
 }
 
+template <class... DS>
 __global__ void bn_bwd_reduce_finalize_kernel(const float* __restrict__ part, int C, int S, float* __restrict__ sum_dy,
-                                              float* __restrict__ sum_dy_xhat) {
+                                              float* __restrict__ sum_dy_xhat, DS... ds) {
+    if constexpr (sizeof...(DS) > 0) {                 // the two-domain layer: this plane's half, statistics row and parameter set
+        const int d = blockIdx.y;
+        const auto& a = dsbn_arg(ds...);
+        part += (int64_t)d * C * S * 2;
+        sum_dy = d ? a.d_beta[1] : a.d_beta[0], sum_dy_xhat = d ? a.d_gamma[1] : a.d_gamma[0];
+    }
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     float a = 0.f, b = 0.f;
@@ -329,6 +397,7 @@ __global__ void bn_bwd_reduce_finalize_kernel(const float* __restrict__ part, in
 }
 
 // dx = gamma*invstd * (g - train*(sum_dy/cnt + xhat*sum_dy_xhat/cnt)),  g = dy*act'(y);  dres = g
+template <class... DS>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                            const float* __restrict__ yact,
                                                            const float* __restrict__ mean,
@@ -338,7 +407,18 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
                                                            const float* __restrict__ sum_dy_xhat,
                                                            float* __restrict__ dx, float* __restrict__ dres,
                                                            int64_t total, int C, int HW, float inv_count, int train,
-                                                           int stat_is_var, float eps, int act, float slope) {
+                                                           int stat_is_var, float eps, int act, float slope, DS... ds) {
+    if constexpr (sizeof...(DS) > 0) {                 // the two-domain layer: this plane's half, statistics row and parameter set
+        const int d = blockIdx.y;
+        const auto& a = dsbn_arg(ds...);
+        const int64_t o = d * total;
+        x += o, dy += o, mean += d * C, invstd += d * C;
+        if (yact) yact += o;
+        if (dx) dx += o;
+        if (dres) dres += o;
+        gamma = d ? a.gamma[1] : a.gamma[0];
+        sum_dy = d ? a.d_beta[1] : a.d_beta[0], sum_dy_xhat = d ? a.d_gamma[1] : a.d_gamma[0];
+    }
     const bool vec = (HW & 3) == 0;
     const int64_t nitems = vec ? (total >> 2) : total;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nitems; i += (int64_t)gridDim.x * blockDim.x) {
@@ -706,12 +786,22 @@ __device__ __forceinline__ void bn_channel_fwd(const float* __restrict__ x, cons
     }
 }
 
+template <class... DS>
 __global__ __launch_bounds__(256) void bn_train_fwd_fused_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                                  const float* __restrict__ beta, const float* __restrict__ res,
                                                                  float* __restrict__ y, float* __restrict__ mean_out,
                                                                  float* __restrict__ invstd_out, float* __restrict__ running_mean,
                                                                  float* __restrict__ running_var, int N, int C, int HW, float eps,
-                                                                 float momentum, int act, float slope) {
+                                                                 float momentum, int act, float slope, DS... ds) {
+    if constexpr (sizeof...(DS) > 0) {                 // the two-domain layer: this plane's half, statistics row and parameter set
+        const int d = blockIdx.y;
+        const auto& a = dsbn_arg(ds...);
+        const DsbnSet p = d ? a.s[1] : a.s[0];
+        const int64_t o = (int64_t)d * N * C * HW;
+        x += o, y += o, mean_out += d * C, invstd_out += d * C;
+        if (res) res += o;
+        gamma = p.gamma, beta = p.beta, running_mean = p.running_mean, running_var = p.running_var, eps = p.eps, momentum = p.momentum;
+    }
     __shared__ float red[4];
     bn_channel_fwd(x, gamma, beta, res, y, mean_out, invstd_out, running_mean, running_var, N, C, HW, eps, momentum, act, slope,
                    (int)blockIdx.x, (int)blockIdx.x, red);
@@ -751,13 +841,22 @@ __device__ __forceinline__ void bn_unit_offsets(unsigned (&off)[U], int t, int t
     }
 }
 
-template <int U>
+template <int U, class... DS>
 __global__ __launch_bounds__(256) void bn_train_fwd_reg_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, const float* __restrict__ res,
                                                                float* __restrict__ y, float* __restrict__ mean_out,
                                                                float* __restrict__ invstd_out, float* __restrict__ running_mean,
                                                                float* __restrict__ running_var, int N, int C, int HW, float eps,
-                                                               float momentum, int act, float slope, unsigned bytes) {
+                                                               float momentum, int act, float slope, unsigned bytes, DS... ds) {
+    if constexpr (sizeof...(DS) > 0) {                 // the two-domain layer: this plane's half, statistics row and parameter set
+        const int d = blockIdx.y;
+        const auto& a = dsbn_arg(ds...);
+        const DsbnSet p = d ? a.s[1] : a.s[0];
+        const int64_t o = (int64_t)d * N * C * HW;
+        x += o, y += o, mean_out += d * C, invstd_out += d * C;
+        if (res) res += o;
+        gamma = p.gamma, beta = p.beta, running_mean = p.running_mean, running_var = p.running_var, eps = p.eps, momentum = p.momentum;
+    }
     __shared__ float red[4];
     const int c = blockIdx.x, t = threadIdx.x;
     const int rl = HW >> 2;
@@ -807,13 +906,24 @@ __global__ __launch_bounds__(256) void bn_train_fwd_reg_kernel(const float* __re
     }
 }
 
-template <int U>
+template <int U, class... DS>
 __global__ __launch_bounds__(256) void bn_train_bwd_reg_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                                const float* __restrict__ yact, const float* __restrict__ mean,
                                                                const float* __restrict__ invstd, const float* __restrict__ gamma,
                                                                float* __restrict__ dx, float* __restrict__ dres,
                                                                float* __restrict__ sum_dy, float* __restrict__ sum_dy_xhat, int N,
-                                                               int C, int HW, int act, float slope, unsigned bytes) {
+                                                               int C, int HW, int act, float slope, unsigned bytes, DS... ds) {
+    if constexpr (sizeof...(DS) > 0) {                 // the two-domain layer: this plane's half, statistics row and parameter set
+        const int d = blockIdx.y;
+        const auto& a = dsbn_arg(ds...);
+        const int64_t o = (int64_t)d * N * C * HW;
+        x += o, dy += o, mean += d * C, invstd += d * C;
+        if (yact) yact += o;
+        if (dx) dx += o;
+        if (dres) dres += o;
+        gamma = d ? a.gamma[1] : a.gamma[0];
+        sum_dy = d ? a.d_beta[1] : a.d_beta[0], sum_dy_xhat = d ? a.d_gamma[1] : a.d_gamma[0];
+    }
     __shared__ float red[4];
     const int c = blockIdx.x, t = threadIdx.x;
     const int rl = HW >> 2;
@@ -1345,12 +1455,24 @@ __device__ __forceinline__ void bn_channel_bwd(const float* __restrict__ x, cons
     }
 }
 
+template <class... DS>
 __global__ __launch_bounds__(256) void bn_train_bwd_fused_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                                  const float* __restrict__ yact, const float* __restrict__ mean,
                                                                  const float* __restrict__ invstd, const float* __restrict__ gamma,
                                                                  float* __restrict__ dx, float* __restrict__ dres,
                                                                  float* __restrict__ sum_dy, float* __restrict__ sum_dy_xhat, int N,
-                                                                 int C, int HW, int act, float slope) {
+                                                                 int C, int HW, int act, float slope, DS... ds) {
+    if constexpr (sizeof...(DS) > 0) {                 // the two-domain layer: this plane's half, statistics row and parameter set
+        const int d = blockIdx.y;
+        const auto& a = dsbn_arg(ds...);
+        const int64_t o = (int64_t)d * N * C * HW;
+        x += o, dy += o, mean += d * C, invstd += d * C;
+        if (yact) yact += o;
+        if (dx) dx += o;
+        if (dres) dres += o;
+        gamma = d ? a.gamma[1] : a.gamma[0];
+        sum_dy = d ? a.d_beta[1] : a.d_beta[0], sum_dy_xhat = d ? a.d_gamma[1] : a.d_gamma[0];
+    }
     __shared__ float red[4];
     bn_channel_bwd(x, dy, yact, mean, invstd, gamma, dx, dres, sum_dy, sum_dy_xhat, N, C, HW, act, slope, (int)blockIdx.x,
                    (int)blockIdx.x, red);
@@ -1976,4 +2098,123 @@ extern "C" int rg_ibn_bwd(const float* x, const float* dy, const float* y_act, c
         hipLaunchKernelGGL(rows_sum_pair_kernel, dim3(rg::cdiv(C, 16)), dim3(256), 0, stream, row_s1, row_s2, d_in_beta, d_in_gamma, N,
                            C, half, d_bn_beta, d_bn_gamma);
     return rg::check_launch("rg_ibn_bwd");
+}
+
+// ---- domain-specific BatchNorm: entry points ----------------------------------------------------------------------------------------
+// Regime by the per-domain extent h*HW alone, h = N / 2: one launch per direction (2C workgroups) when h*HW <= 16384; otherwise slice
+// partial + finalize + apply over both domains at once — three launches, as ONE BatchNorm.  No channel threshold as in
+// rg_bn_train_fused_ok: the two-pass statistics of the one-launch kernels do not depend on how many values a thread is left with,
+// while the slice kernels at a handful of values per thread merge single-value statistics and lose accuracy when |mean| >> std.
+// (Whether three launches would be faster for few channels at the largest such extent, e.g. C = 64 on 128 workgroups, is not measured.)
+
+static bool dsbn_one_launch(int h, int C, int HW) { return (int64_t)h * HW <= 16384; }
+
+// slices of one domain's h*HW values: as many workgroups as a BatchNorm over 2C channels would start
+static int dsbn_slices(int h, int C, int HW, int* L) { return pick_slices(h, 2 * C, HW, L); }
+
+// bytes of workspace for rg_dsbn_fwd / rg_dsbn_bwd: the slice partials [2][C][S][3] (0 for an invalid geometry)
+extern "C" int64_t rg_dsbn_workspace(int N, int C, int HW) {
+    if (N <= 0 || (N & 1) || C <= 0 || HW <= 0) return 0;
+    int L;
+    const int S = dsbn_slices(N / 2, C, HW, &L);
+    return (int64_t)((size_t)2 * C * S * 3 * sizeof(float));
+}
+
+// 1: one launch per direction, 0: the slice regime (rg_dsbn_slices slices per domain)
+extern "C" int rg_dsbn_one_launch(int N, int C, int HW) { return N > 0 && !(N & 1) && dsbn_one_launch(N / 2, C, HW) ? 1 : 0; }
+
+// float4 units per thread the one-workgroup-per-channel kernels run with for N samples (what rg_bn_train_*_fused and, with N / 2,
+// rg_dsbn_* launch): 1, 2, 4, 8, 16 = the register kernels, 0 = the loop kernels (scalar rows, more than 16 units, or RG_BN_REG=0)
+extern "C" int rg_bn_reg_units(int N, int C, int HW) { return g_bn_reg && N > 0 && C > 0 && HW > 0 ? bn_reg_units(N, C, HW) : 0; }
+
+extern "C" int rg_dsbn_slices(int N, int C, int HW) {
+    if (N <= 0 || (N & 1) || C <= 0 || HW <= 0) return 0;
+    int L;
+    return dsbn_slices(N / 2, C, HW, &L);
+}
+
+extern "C" int rg_dsbn_fwd(const float* x, const float* gamma_s, const float* beta_s, const float* gamma_t, const float* beta_t,
+                           const float* residual, float* y, float* mean, float* invstd, float* running_mean_s, float* running_var_s,
+                           float* running_mean_t, float* running_var_t, int N, int C, int HW, float eps_s, float eps_t,
+                           float momentum_s, float momentum_t, int act, float slope, void* workspace, size_t workspace_bytes,
+                           hipStream_t stream) {
+    RG_REQUIRE(x && y && mean && invstd && N > 0 && C > 0 && HW > 0, "rg_dsbn_fwd: bad arguments");
+    RG_REQUIRE((N & 1) == 0, "rg_dsbn_fwd: the batch of %d samples has no [source | target] halves", N);
+    const int h = N / 2;
+    RG_REQUIRE((int64_t)h * HW < (1ll << 30) && (int64_t)2 * C < (1ll << 16), "rg_dsbn_fwd: N*HW or C too large");
+    const DsbnFwd a = {{{gamma_s, beta_s, running_mean_s, running_var_s, eps_s, momentum_s},
+                        {gamma_t, beta_t, running_mean_t, running_var_t, eps_t, momentum_t}}};
+    const float* no = nullptr;                           // per-domain arguments of the BatchNorm kernels: taken from `a` in the kernel
+    float* non = nullptr;
+    const int64_t half_total = (int64_t)h * C * HW;
+    rg::ProfScope prof(rg::FAM_NORM, stream, 0.0, (residual ? 12.0 : 8.0) * 2.0 * (double)half_total);
+    if (dsbn_one_launch(h, C, HW)) {                     // the BatchNorm kernels over h samples, grid (C, 2)
+        const unsigned bytes = (unsigned)(half_total * 4);
+        if (!with_lanes_units(BnUnits{}, 256, g_bn_reg ? bn_reg_units(h, C, HW) : 0, [&](auto, auto U) {
+                hipLaunchKernelGGL(bn_train_fwd_reg_kernel<U>, dim3(C, 2), dim3(256), 0, stream, x, no, no, residual, y, mean, invstd, non,
+                                   non, h, C, HW, 0.f, 0.f, act, slope, bytes, a);
+            }))
+            hipLaunchKernelGGL(bn_train_fwd_fused_kernel, dim3(C, 2), dim3(256), 0, stream, x, no, no, residual, y, mean, invstd, non, non,
+                               h, C, HW, 0.f, 0.f, act, slope, a);
+        return rg::check_launch("rg_dsbn_fwd");
+    }
+    int L;
+    const int S = dsbn_slices(h, C, HW, &L);
+    if (!workspace || workspace_bytes < (size_t)2 * C * S * 3 * sizeof(float)) {
+        rg::set_error("rg_dsbn_fwd: workspace too small");
+        return RG_ERR_WORKSPACE;
+    }
+    float* part = static_cast<float*>(workspace);
+    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(S, C, 2), dim3(256), 0, stream, x, part, h, C, HW, L, DsbnPlane{});
+    hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(rg::cdiv(C, 64), 2), dim3(64), 0, stream, (const float*)part, C, S, 0.f, 0.f, mean,
+                       invstd, non, non, a);
+    hipLaunchKernelGGL(bn_apply_fwd_kernel, dim3(grid_for((HW & 3) ? half_total : half_total / 4), 2), dim3(256), 0, stream, x,
+                       (const float*)mean, (const float*)invstd, no, no, residual, y, half_total, C, HW, 0, 0.f, act, slope, a);
+    return rg::check_launch("rg_dsbn_fwd");
+}
+
+// dx, dres (either may be NULL) and the four affine gradients (outputs: the channel sums are written straight into them).
+// mean / invstd [2][C] as rg_dsbn_fwd wrote them.
+extern "C" int rg_dsbn_bwd(const float* x, const float* dy, const float* y_act, const float* mean, const float* invstd,
+                           const float* gamma_s, const float* gamma_t, float* dx, float* dres, float* d_gamma_s, float* d_beta_s,
+                           float* d_gamma_t, float* d_beta_t, int N, int C, int HW, int act, float slope, void* workspace,
+                           size_t workspace_bytes, hipStream_t stream) {
+    RG_REQUIRE(x && dy && mean && invstd && N > 0 && C > 0 && HW > 0, "rg_dsbn_bwd: bad arguments");
+    RG_REQUIRE(d_gamma_s && d_beta_s && d_gamma_t && d_beta_t, "rg_dsbn_bwd: the four affine gradients are outputs");
+    RG_REQUIRE((N & 1) == 0, "rg_dsbn_bwd: the batch of %d samples has no [source | target] halves", N);
+    RG_REQUIRE(act == RG_ACT_NONE || y_act, "rg_dsbn_bwd: fused activation needs the forward output");
+    const int h = N / 2;
+    RG_REQUIRE((int64_t)h * HW < (1ll << 30) && (int64_t)2 * C < (1ll << 16), "rg_dsbn_bwd: N*HW or C too large");
+    const DsbnBwd a = {{gamma_s, gamma_t}, {d_gamma_s, d_gamma_t}, {d_beta_s, d_beta_t}};
+    const float* no = nullptr;                           // gamma and the sums: taken from `a` in the kernel
+    float* non = nullptr;
+    const int64_t half_total = (int64_t)h * C * HW;
+    rg::ProfScope prof(rg::FAM_NORM, stream, 0.0,
+                       ((act ? 12.0 : 8.0) + (dx ? 4.0 : 0.0) + (dres ? 4.0 : 0.0)) * 2.0 * (double)half_total);
+    if (dsbn_one_launch(h, C, HW)) {
+        const unsigned bytes = (unsigned)(half_total * 4);
+        if (!with_lanes_units(BnUnits{}, 256, g_bn_reg ? bn_reg_units(h, C, HW) : 0, [&](auto, auto U) {
+                hipLaunchKernelGGL(bn_train_bwd_reg_kernel<U>, dim3(C, 2), dim3(256), 0, stream, x, dy, y_act, mean, invstd, no, dx, dres,
+                                   non, non, h, C, HW, act, slope, bytes, a);
+            }))
+            hipLaunchKernelGGL(bn_train_bwd_fused_kernel, dim3(C, 2), dim3(256), 0, stream, x, dy, y_act, mean, invstd, no, dx, dres, non,
+                               non, h, C, HW, act, slope, a);
+        return rg::check_launch("rg_dsbn_bwd");
+    }
+    int L;
+    const int S = dsbn_slices(h, C, HW, &L);
+    if (!workspace || workspace_bytes < (size_t)2 * C * S * 2 * sizeof(float)) {
+        rg::set_error("rg_dsbn_bwd: workspace too small");
+        return RG_ERR_WORKSPACE;
+    }
+    float* part = static_cast<float*>(workspace);
+    hipLaunchKernelGGL(bn_bwd_reduce_partial_kernel, dim3(S, C, 2), dim3(256), 0, stream, x, dy, y_act, mean, invstd, part, h, C, HW, L,
+                       0, 0.f, act, slope, DsbnPlane{});
+    hipLaunchKernelGGL(bn_bwd_reduce_finalize_kernel, dim3(rg::cdiv(C, 64), 2), dim3(64), 0, stream, (const float*)part, C, S, non, non,
+                       a);
+    if (dx || dres)
+        hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for((HW & 3) ? half_total : half_total / 4), 2), dim3(256), 0, stream, x, dy,
+                           y_act, mean, invstd, no, no, no, dx, dres, half_total, C, HW, 1.f / (float)((int64_t)h * HW), 1, 0, 0.f, act,
+                           slope, a);
+    return rg::check_launch("rg_dsbn_bwd");
 }

@@ -83,7 +83,7 @@ def build(verbose=False):
     return LIB_PATH
 
 
-PLAIN_INT = {"rg_version", "rg_family_count", "rg_fold_chunk", "rg_bn_slices", "rg_conv2d_dgrad_rowsum_cols", "rg_f8_grad_tiles", "rg_krsc_chunk", "rg_conv_set_planes", "rg_conv_tune_stats", "rg_conv_splitk_inkernel_count", "rg_conv_set_pick", "rg_conv_pick_log"}   # int-returning queries that are not status codes
+PLAIN_INT = {"rg_version", "rg_family_count", "rg_fold_chunk", "rg_bn_slices", "rg_dsbn_one_launch", "rg_dsbn_slices", "rg_bn_reg_units", "rg_conv2d_dgrad_rowsum_cols", "rg_f8_grad_tiles", "rg_krsc_chunk", "rg_conv_set_planes", "rg_conv_tune_stats", "rg_conv_splitk_inkernel_count", "rg_conv_set_pick", "rg_conv_pick_log"}   # int-returning queries that are not status codes
 
 
 class _Lib(object):

@@ -496,9 +496,17 @@ class _Fold(object):
     __slots__ = ("key", "scale", "shift", "invstd", "w_scaled", "w_scaled_krsc")
 
 
+def _fold_bn(bn):
+    """the BatchNorm whose running statistics and affine parameters make the eval-mode map of `bn`: a DSBN layer in eval mode IS
+    its BN_T (CC/clustercontrast/models/dsbn.py:14-15); every other module stands for itself"""
+    return bn.BN_T if isinstance(bn, _DSBN) else bn
+
+
 def _foldable(conv, bn):
-    return (isinstance(bn, _BatchNorm) and not bn.training and bn.track_running_stats and bn.affine and conv.bias is None
-            and isinstance(conv, Conv2d))
+    own = bn                                             # a DSBN layer's own mode decides; its BN_T supplies the map
+    bn = _fold_bn(bn)
+    return (isinstance(bn, _BatchNorm) and not own.training and not bn.training and bn.track_running_stats and bn.affine
+            and conv.bias is None and isinstance(conv, Conv2d))
 
 
 _FOLD_IN_CAPTURE = ("a network that folds BatchNorm into its convolutions cannot be captured: a replay would keep the filters "
@@ -508,6 +516,7 @@ _FOLD_IN_CAPTURE = ("a network that folds BatchNorm into its convolutions cannot
 def _fold_key(conv, bn):
     """weight_key of the five tensors a fold is made from (read from the modules' own dicts: nn.Module.__getattr__ per tensor would
     cost several times the key, and conv_bn_tf asks on every call)"""
+    bn = _fold_bn(bn)
     p, b = bn._parameters, bn._buffers
     return weight_key(conv._parameters["weight"], p["weight"], p["bias"], b["running_mean"], b["running_var"])
 
@@ -516,6 +525,7 @@ def _fold_of(conv, bn):
     """Per-pair fold (one small launch group); networks fold all their pairs at once through FoldGroup."""
     if ops.CAPTURING[0]:
         raise RuntimeError(_FOLD_IN_CAPTURE)
+    bn = _fold_bn(bn)
     key = _fold_key(conv, bn)
     f = getattr(conv, "_rg_fold", None)
     if f is None or f.key != key:
@@ -533,7 +543,7 @@ class FoldGroup(object):
     (`rg_fold_filters_multi`): scale / shift / invstd and the scaled filters of every pair live in two flat buffers."""
 
     def __init__(self, pairs):
-        self.pairs = list(pairs)
+        self.pairs = [(conv, _fold_bn(bn)) for conv, bn in pairs]
         self.keys = None                  # per pair: _fold_key its fold in `folds` was made for
         self.ptrs = None                  # per pair: the five input addresses `table` holds
 
@@ -627,6 +637,7 @@ def conv_bn_tb(tape, conv, bn, dy, need_dx=True, residual=None, dy_masked=False,
     if want_rowsum is None:
         want_rowsum = mask_input and tape.param_grad      # the layer below is a fold that will want the channel sums
     x, y, f, act, has_res = rec
+    bn = _fold_bn(bn)
     want_w, want_g, want_b = tape.wants(conv.weight), tape.wants(bn.weight), tape.wants(bn.bias)
     need_sum = want_g or want_b
     ob = tape.grad_out(bn.bias) if want_b else None
@@ -683,6 +694,63 @@ class BatchNorm2d(_BatchNorm):
 
 class BatchNorm1d(_BatchNorm):
     pass
+
+
+class _DSBN(RGModule):
+    """Domain-specific BatchNorm (CC/clustercontrast/models/dsbn.py:6-42): a train-mode batch is [source half | target half] and
+    each half is normalised with its own batch statistics, affine parameters and running statistics; eval mode is `BN_T` on the
+    whole batch.  The children `BN_S` / `BN_T` only hold the parameters and buffers (so the reference's keys `...BN_S.weight`,
+    `...BN_T.running_mean` load unchanged); the train-mode arithmetic is `rg_dsbn_fwd` / `rg_dsbn_bwd` on the ONE tensor — no
+    split copies, no concatenation.  `tf` / `tb` have `_BatchNorm`'s signatures."""
+    _bn_cls = None
+
+    def __init__(self, planes):
+        super(_DSBN, self).__init__()
+        self.num_features = planes
+        self.BN_S = self._bn_cls(planes)
+        self.BN_T = self._bn_cls(planes)
+
+    def tf(self, tape, x, residual=None, act=ACT_NONE, slope=0.0):
+        s, t = self.BN_S, self.BN_T
+        if not self.training:
+            y = t.tf(tape, x, residual=residual, act=act, slope=slope)
+            tape.push(None)
+            return y
+        if x.shape[0] % 2:
+            raise AssertionError("DSBN: a train-mode batch is [source half | target half]; got %d samples" % x.shape[0])
+        for bn in (s, t):
+            bn.__dict__["_nbt_pending"] = bn.__dict__.get("_nbt_pending", 0) + 1          # as _BatchNorm.tf
+        y, stats = ops.dsbn_fwd(x, s.weight.detach(), s.bias.detach(), t.weight.detach(), t.bias.detach(),
+                                (s.running_mean, s.running_var), (t.running_mean, t.running_var), (s.eps, t.eps),
+                                (s.momentum, t.momentum), residual=residual, act=act, slope=slope)
+        tape.push((x, y if act != ACT_NONE else None, stats, act, slope, residual is not None))
+        return y
+
+    def tb(self, tape, dy, need_dx=True, dy_masked=False):
+        """dy_masked: the consumer's dgrad already applied this layer's ReLU mask (see _BatchNorm.tb): y is not read."""
+        rec = tape.pop()
+        if rec is None:
+            return self.BN_T.tb(tape, dy, need_dx=need_dx, dy_masked=dy_masked)
+        x, y, stats, act, slope, has_res = rec
+        if dy_masked:
+            act, y = ACT_NONE, None
+        s, t = self.BN_S, self.BN_T
+        params = (s.weight, s.bias, t.weight, t.bias)
+        out = tuple(tape.grad_out(p) if tape.wants(p) else None for p in params)
+        res = ops.dsbn_bwd(x, dy, y, stats, s.weight.detach(), t.weight.detach(), act, slope, need_dx=need_dx or not has_res,
+                           need_dres=has_res, out=out)
+        for p, g in zip(params, res[2:]):
+            if tape.wants(p):
+                tape.add_grad(p, g)
+        return (res[0], res[1]) if has_res else res[0]
+
+
+class DSBN2d(_DSBN):
+    _bn_cls = BatchNorm2d
+
+
+class DSBN1d(_DSBN):
+    _bn_cls = BatchNorm1d
 
 
 class _Act(RGModule):

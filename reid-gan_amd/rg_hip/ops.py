@@ -602,6 +602,43 @@ def ibn_bwd(x, dy, y_act, half, in_mean, in_invstd, bn_mean, bn_stat, in_gamma, 
     return (dx,) + tuple(grads)
 
 
+def dsbn_fwd(x, gamma_s, beta_s, gamma_t, beta_t, running_s=(None, None), running_t=(None, None), eps=(1e-5, 1e-5),
+             momentum=(0.1, 0.1), residual=None, act=ACT_NONE, slope=0.0):
+    """train-mode domain-specific BatchNorm on the whole [source | target] batch, no slice / cat copies: samples [0, N/2) with
+    their batch statistics and the S set, samples [N/2, N) with theirs and the T set; running_s / running_t = (mean, var), updated
+    in place -> (y, stats[2][2][C]): stats[0] the two means, stats[1] the two invstd (S row, T row)."""
+    if x.shape[0] % 2:
+        raise RuntimeError("dsbn_fwd: a batch of %d samples has no [source | target] halves" % x.shape[0])
+    x, residual = _chk(x, "x"), _chk(residual, "residual")
+    _same_size("dsbn_fwd", x, residual=residual)
+    N, C, HW = _nchw(x)
+    y = torch.empty_like(x)
+    stats = torch.empty(2, 2, C, dtype=torch.float32, device=x.device)
+    ws = workspace(_ws_query("rg_dsbn_workspace", N, C, HW), x.device)
+    lib.rg_dsbn_fwd(_p(x), _p(gamma_s), _p(beta_s), _p(gamma_t), _p(beta_t), _p(residual), _p(y), _p(stats[0]), _p(stats[1]),
+                    _p(running_s[0]), _p(running_s[1]), _p(running_t[0]), _p(running_t[1]), N, C, HW, eps[0], eps[1], momentum[0],
+                    momentum[1], act, slope, _p(ws), ws.numel(), _stream())
+    return y, stats
+
+
+def dsbn_bwd(x, dy, y_act, stats, gamma_s, gamma_t, act=ACT_NONE, slope=0.0, need_dx=True, need_dres=False,
+             out=(None, None, None, None)):
+    """-> (dx, dres, d_gamma_s, d_beta_s, d_gamma_t, d_beta_t).  stats: what dsbn_fwd returned.  `out`: preallocated gradient
+    outputs in that order."""
+    if x.shape[0] % 2:
+        raise RuntimeError("dsbn_bwd: a batch of %d samples has no [source | target] halves" % x.shape[0])
+    x, dy, y_act = _chk(x, "x"), _chk(dy, "dy"), _chk(y_act, "y")
+    _same_size("dsbn_bwd", dy, x=x, y=y_act)
+    N, C, HW = _nchw(x)
+    dx = torch.empty_like(dy) if need_dx else None
+    dres = torch.empty_like(dy) if need_dres else None
+    grads = [o if o is not None else torch.empty(C, dtype=torch.float32, device=x.device) for o in out]
+    ws = workspace(_ws_query("rg_dsbn_workspace", N, C, HW), x.device)
+    lib.rg_dsbn_bwd(_p(x), _p(dy), _p(y_act), _p(stats[0]), _p(stats[1]), _p(gamma_s), _p(gamma_t), _p(dx), _p(dres), _p(grads[0]),
+                    _p(grads[1]), _p(grads[2]), _p(grads[3]), N, C, HW, act, slope, _p(ws), ws.numel(), _stream())
+    return (dx, dres) + tuple(grads)
+
+
 def bn_bwd_apply(x, dy, y_act, mean, stat, gamma, sum_dy, sum_dy_xhat, train, stat_is_var=False, eps=1e-5,
                  act=ACT_NONE, slope=0.0, need_dx=True, need_dres=False):
     x, dy, y_act = _chk(x, "x"), _chk(dy, "dy"), _chk(y_act, "y")

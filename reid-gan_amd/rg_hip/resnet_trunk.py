@@ -151,8 +151,8 @@ class IBNResNet(TVResNet):
 
 def _conv_bn_pairs(mods):
     """the (conv, BatchNorm) pairs a FoldGroup folds; an IBN layer is not a per-channel affine map of the conv output (its IN half
-    depends on the sample), so its pair stays on the unfused conv -> IBN path"""
-    return [(conv, bn) for conv, bn in _conv_norm_pairs(mods) if isinstance(bn, rnn._BatchNorm)]
+    depends on the sample), so its pair stays on the unfused conv -> IBN path; a DSBN layer in eval mode is its BN_T"""
+    return [(conv, bn) for conv, bn in _conv_norm_pairs(mods) if isinstance(rnn._fold_bn(bn), rnn._BatchNorm)]
 
 
 def _conv_norm_pairs(mods):
