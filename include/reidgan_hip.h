@@ -405,6 +405,60 @@ int rg_dbscan_labels(const int* rowptr, const int* nbr, const int* parent, int N
                      rg_stream_t stream);
 int rg_dbscan_asymmetry(const void* d, int is_half, int N, int64_t ld, int* count, rg_stream_t stream);
 
+/* ---- Two-level Infomap on a kNN table nbrs int32 / dists fp32 [N][k]: `cluster_by_infomap` of
+ * CC/clustercontrast/utils/infomap_cluster.py:129-227 (the pseudo-labelling step of the infomap example scripts) as the
+ * two-level directed map equation under a deterministic, host-driven search (not the labels of the seeded `infomap`
+ * package).  All index arrays int32, all flows fp64, N <= 65536, k <= 128; every sum runs in a fixed order and only integer
+ * atomics are used whose result does not depend on their order.  A unit graph is two CSR lists (out: orp / odst / oq, in:
+ * irp / isrc / iq, in-lists in ascending source order) plus the unit flows pu; module totals live in slots [0, U).
+ *   rg_infomap_links_count   cnt[i] = links of row i (left to right: self skipped, dist <= thr links, the first other entry or
+ *                            an index outside [0, N) ends the row); rowptr [N + 1] = exclusive prefix sum
+ *   rg_infomap_links_fill    src / dst / w (= double(1.0f - dist)) at rowptr[i] .., single[i] = the row gave no link,
+ *                            incnt[j] = in-links of j, in_rowptr [N + 1] = its prefix sum
+ *   rg_infomap_flow_start    wout / win = link weight out of / into every node, p = uniform over the nodes in a link,
+ *                            tele = win / total, scal [16] = the iteration's fp64 scalars ([4] L1 change, [5] iterations,
+ *                            [6] done, [7] sum_nodes plogp(flow) after rg_infomap_flow_finish)
+ *   rg_infomap_flow_iterate  `iters` PageRank steps (alpha 0.15, teleportation to links, dangling nodes teleport with
+ *                            probability 1); a step after the L1 change fell to 1e-13 or max_iters were run changes nothing
+ *   rg_infomap_flow_finish   q[e] = p_src w_e / wout_src normalised to sum 1, iq = q in in-list order, flow[j] = in-flow
+ *   rg_infomap_totals        xo / xi = flow of every unit's links that cross modules; per module (segments of `order`, a
+ *                            stable sort of mod) exit / enter / flow / unit count into slot mod (zero the slots first)
+ *   rg_infomap_codelength    out[0] = plogp(sum enter) - sum plogp(enter) - sum plogp(exit) + sum plogp(exit + flow) -
+ *                            *nodeterm in bits, out[1] = sum enter
+ *   rg_infomap_propose       per unit the best move to the module of a linked unit against the frozen totals (gain > 1e-10
+ *                            bits, ties to the lower module): tgt (-1: none), key = (gain bits, unit), vals = the new exit /
+ *                            enter of both modules; claim[m] / *best = highest key per module / overall
+ *   rg_infomap_apply         single 0: every unit whose key holds both its modules moves and writes their totals; single 1:
+ *                            only the unit holding *best; *nmoved = moves
+ *   rg_infomap_segment_sum   out[s] = sum of q[eidx[t]], t in [segptr[s], segptr[s + 1]), front to back
+ *   rg_infomap_labels        modules with more than cluster_num members numbered by ascending smallest member, -1 for the
+ *                            rest; num[N] = number of kept modules */
+int rg_infomap_links_count(const int* nbrs, const float* dists, int N, int k, float thr, int* cnt, int* rowptr, rg_stream_t stream);
+int rg_infomap_links_fill(const int* nbrs, const float* dists, int N, int k, float thr, const int* rowptr, int* src, int* dst,
+                          double* w, int* single, int* incnt, int* in_rowptr, rg_stream_t stream);
+int rg_infomap_flow_start(const int* orp, const double* w, const int* irp, const int* ieid, int N, int E, double* wout, double* win,
+                          double* p, double* tele, double* scal, rg_stream_t stream);
+int rg_infomap_flow_iterate(const int* orp, const int* irp, const int* isrc, const int* ieid, const double* w, const double* wout,
+                            const double* tele, int N, int E, int iters, int max_iters, double* p, double* raw, double* scal,
+                            rg_stream_t stream);
+int rg_infomap_flow_finish(const int* src, const int* irp, const int* ieid, const double* w, const double* wout, const double* p,
+                           int N, int E, double* q, double* iq, double* flow, double* scal, rg_stream_t stream);
+int rg_infomap_totals(const int* orp, const int* odst, const double* oq, const int* irp, const int* isrc, const double* iq,
+                      const double* pu, const int* mod, const int* order, const int* segptr, int U, int S, double* xo, double* xi,
+                      double* mexit, double* menter, double* mflow, int* nunits, rg_stream_t stream);
+int rg_infomap_codelength(const double* mexit, const double* menter, const double* mflow, int M, const double* nodeterm, double* out,
+                          rg_stream_t stream);
+int rg_infomap_propose(const int* orp, const int* odst, const double* oq, const int* irp, const int* isrc, const double* iq,
+                       const double* pu, const int* mod, const double* mexit, const double* menter, const double* mflow,
+                       const int* nunits, int U, const double* cl, int* tgt, void* key, double* vals, void* claim, void* best,
+                       int* nmoved, rg_stream_t stream);
+int rg_infomap_apply(const int* tgt, const void* key, const double* vals, const void* claim, const void* best, const double* pu,
+                     int U, int single, int* mod, double* mexit, double* menter, double* mflow, int* nunits, int* nmoved,
+                     rg_stream_t stream);
+int rg_infomap_segment_sum(const double* q, int E, const int* eidx, const int* segptr, int S, int T, double* out, rg_stream_t stream);
+int rg_infomap_labels(const int* mod, int N, int cluster_num, int* size, int* minm, int* head, int* num, int64_t* labels,
+                      rg_stream_t stream);
+
 /* ---- CMC / mAP scoring of a query x gallery distance matrix dist [Q][ld] (fp32, or fp64 with is_double = 1; compared in its
  * own type), CC/clustercontrast/evaluation_metrics/ranking.py `cmc` / `mean_ap`, without a sort.  All id / camera arrays int32.
  * Per query i: valid_j = (gid_j != qid_i) | (gcam_j != qcam_i) (and gcam_j != qcam_i with separate_camera_set), pos_j = valid_j

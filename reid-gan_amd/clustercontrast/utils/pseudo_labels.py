@@ -8,6 +8,9 @@ becomes `pseudo_labels, num_cluster, cluster_features = dbscan_pseudo_labels(fea
 neither copied to the host nor duplicated; only the N labels come back, because the caller builds its dataset list from them
 (:195-198).  `cluster_features` is the un-normalised per-cluster mean in ascending label order, ready for
 `F.normalize(cluster_features, dim=1)` into `ClusterMemory.features`.
+
+`infomap_pseudo_labels` is the same for examples/cluster_contrast_gan_train_usl_infomap.py:318-348 (normalise, get_dist_nbr,
+cluster_by_infomap, generate_cluster_features): kNN table, Infomap and centroids stay on the device.
 """
 from __future__ import absolute_import, print_function
 
@@ -17,7 +20,7 @@ import torch
 
 from rg_hip import ops
 from .faiss_rerank import compute_jaccard_distance
-from .infomap_cluster import generate_cluster_features_device
+from .infomap_cluster import cluster_by_infomap, generate_cluster_features_device, get_dist_nbr
 
 
 @torch.no_grad()
@@ -43,3 +46,30 @@ def dbscan_pseudo_labels(features, k1=30, k2=6, eps=0.6, min_samples=4, print_fl
         print("DBSCAN pseudo labels: {} clusters, {} outliers, time cost: {}".format(
             num_cluster, int((pseudo_labels == -1).sum()), time.time() - end))
     return pseudo_labels, num_cluster, cluster_features
+
+
+@torch.no_grad()
+def infomap_pseudo_labels(features, k=15, min_sim=0.5, cluster_num=4, print_flag=False):
+    """(pseudo_labels numpy int64 [N], cluster_features device tensor [C, D], info) of `features` [N, D] (host or device
+    tensor): the rows are L2-normalised, searched for their k nearest neighbours and clustered by the two-level Infomap of
+    cluster_by_infomap; -1 marks a sample whose cluster has <= cluster_num members.  cluster_features is the un-normalised
+    mean of the normalised rows of every cluster in ascending label order (an empty [0, D] tensor without a cluster).  Only
+    the N labels are copied out.  The defaults are the scripts' --k1 15 --eps 0.5 --k2 4."""
+    end = time.time()
+    x = features if torch.is_tensor(features) else torch.as_tensor(features)
+    if x.dim() != 2:
+        raise ValueError("infomap_pseudo_labels: features must be [N, D], got shape %s" % (tuple(x.shape),))
+    if not torch.cuda.is_available():
+        raise RuntimeError("infomap_pseudo_labels: features must live on the GPU; the HIP path has no CPU fallback")
+    x = torch.nn.functional.normalize(x.float().to(torch.device("cuda", torch.cuda.current_device())), dim=1).contiguous()
+    dists, nbrs = get_dist_nbr(x, k=int(k), knn_method='faiss-gpu', return_device=True)
+    labels, info = cluster_by_infomap(nbrs, dists, min_sim=min_sim, cluster_num=cluster_num, return_device=True, return_info=True)
+    if info["n_clusters"]:
+        cluster_features = generate_cluster_features_device(labels, x)
+    else:
+        cluster_features = torch.empty((0, x.shape[1]), dtype=torch.float32, device=labels.device)
+    pseudo_labels = labels.cpu().numpy()
+    if print_flag:
+        print("Infomap pseudo labels: {} clusters, {} outliers, codelength {:.4f} bits, time cost: {}".format(
+            info["n_clusters"], int((pseudo_labels == -1).sum()), info["codelength"], time.time() - end))
+    return pseudo_labels, cluster_features, info

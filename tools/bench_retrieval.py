@@ -19,7 +19,14 @@ the host-loop generate_cluster_features, on the host clock (skipped with a note 
 its fp64 copy (both kernels and the clearing of the outputs) and around a device-to-device copy of the fp32 matrix as the
 bandwidth yardstick, one warm-up pass, median of `--reps`; the wall time of `ops.rank_eval` with its read-back; and, in the
 same run, the host path it replaces: the device->host copy plus the numpy model (tests/rank_eval_hostmodel.py: a stable
-argsort and one scikit-learn `average_precision_score` call per query, what the reference does twice per evaluation)."""
+argsort and one scikit-learn `average_precision_score` call per query, what the reference does twice per evaluation).
+
+`--infomap [N,D,k[,min_sim[,cluster_num]]] [--noise X]` (default 12936,2048,15,0.5,4: Market-1501's training set and the
+scripts' --k1 15 --eps 0.5 --k2 4) times the Infomap pseudo-labelling on the kNN table of the same clustered synthetic
+features: device events around `links`, `flow`, `search` and `labels` (each with the read-backs its host loop makes), one
+warm-up pass, median of `--reps` (default 30); the counts of sweeps, levels and flow iterations; and the wall time of
+`infomap_pseudo_labels` end to end (normalise + kNN + Infomap + centroids + the N labels to the host).  There is no host
+path to put beside it: the `infomap` package is not part of this environment."""
 import os, sys, time, json
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "reid-gan_amd"))
@@ -151,6 +158,52 @@ def dbscan_mode(spec, reps, noise):
     print(json.dumps(res))
 
 
+def infomap_mode(spec, reps, noise):
+    import numpy as np
+    from clustercontrast.utils.infomap_cluster import get_dist_nbr
+    from clustercontrast.utils.pseudo_labels import infomap_pseudo_labels
+    parts = spec.split(",")
+    N, D, k = (int(v) for v in parts[:3])
+    min_sim = float(parts[3]) if len(parts) > 3 else 0.5
+    cluster_num = int(parts[4]) if len(parts) > 4 else 4
+    x = _clustered_features(N, D, noise)
+    dists, nbrs = get_dist_nbr(x, k=k, return_device=True)
+    names = ["links", "flow", "search", "labels"]
+    samples = {n: [] for n in names}
+    info = {}
+    for it in range(reps + 1):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(names) + 1)]
+        ev[0].record()
+        g = ops.infomap_links(nbrs, dists, min_sim); ev[1].record()
+        g = ops.infomap_flow(g); ev[2].record()
+        modules, stats = ops.infomap_search(g); ev[3].record()
+        labels, n_clusters = ops.infomap_labels(modules, cluster_num); ev[4].record()
+        torch.cuda.synchronize()
+        if it:                                   # pass 0 is the warm-up
+            for i, n in enumerate(names):
+                samples[n].append(ev[i].elapsed_time(ev[i + 1]))
+        info = {"links": g["E"], "row_mean": round(g["E"] / N, 1), "singles": int(g["single"].sum()), "flow_iterations": g["flow_iterations"],
+                "sweeps": stats["sweeps"], "levels": stats["levels"], "rounds": stats["rounds"], "moves": stats["moves"],
+                "rollbacks": stats["rollbacks"], "converged": bool(stats["converged"]), "n_modules": stats["n_modules"],
+                "n_clusters": n_clusters, "outliers": int((labels < 0).sum()),
+                "codelength_bits": ops.infomap_codelength(g, modules),
+                "codelength_one_module_bits": ops.infomap_codelength(g, torch.zeros_like(modules))}
+    med = {n: round(float(np.median(v)), 3) for n, v in samples.items()}
+    wall = []
+    for it in range(min(reps, 5) + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        infomap_pseudo_labels(x, k=k, min_sim=min_sim, cluster_num=cluster_num)
+        torch.cuda.synchronize()
+        if it:
+            wall.append((time.perf_counter() - t0) * 1e3)
+    res = {"infomap": {"N": N, "D": D, "k": k, "min_sim": min_sim, "cluster_num": cluster_num, "noise": noise, "reps": reps},
+           "stage_ms_median": med, "stage_ms_min_max": {n: [round(min(v), 3), round(max(v), 3)] for n, v in samples.items()},
+           "infomap_total_ms": round(sum(med.values()), 3), "pseudo_labels_end_to_end_wall_ms": round(float(np.median(wall)), 3)}
+    res.update(info)
+    print(json.dumps(res))
+
+
 def evaluate_mode(spec, reps, noise):
     import numpy as np
     from rg_hip.lib import lib
@@ -229,6 +282,14 @@ if "--evaluate" in sys.argv:
     _reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 5
     _noise = float(sys.argv[sys.argv.index("--noise") + 1]) if "--noise" in sys.argv else 0.90
     evaluate_mode(_spec, _reps, _noise)
+    sys.exit(0)
+
+if "--infomap" in sys.argv:
+    _i = sys.argv.index("--infomap") + 1
+    _spec = sys.argv[_i] if _i < len(sys.argv) and not sys.argv[_i].startswith("--") else "12936,2048,15,0.5,4"
+    _reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 30
+    _noise = float(sys.argv[sys.argv.index("--noise") + 1]) if "--noise" in sys.argv else 0.30
+    infomap_mode(_spec, _reps, _noise)
     sys.exit(0)
 
 if "--dbscan" in sys.argv:

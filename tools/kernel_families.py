@@ -77,6 +77,13 @@ FAMILY = {
     # dbscan.hip
     "dbscan_row_kernel": "misc", "dbscan_parent_init_kernel": "misc", "dbscan_hook_kernel": "misc", "dbscan_flatten_kernel": "misc",
     "dbscan_root_flag_kernel": "misc", "dbscan_label_kernel": "misc", "dbscan_asym_kernel": "misc",
+    # infomap.hip
+    "infomap_links_kernel": "misc", "infomap_weights_kernel": "misc", "infomap_flow_start_kernel": "misc",
+    "infomap_flow_pull_kernel": "misc", "infomap_flow_update_kernel": "misc", "infomap_link_flow_kernel": "misc",
+    "infomap_sum_kernel": "misc", "infomap_scale_kernel": "misc", "infomap_node_flow_kernel": "misc", "infomap_cross_kernel": "misc",
+    "infomap_module_totals_kernel": "misc", "infomap_codelength_kernel": "misc", "infomap_propose_kernel": "misc",
+    "infomap_apply_kernel": "misc", "infomap_segment_sum_kernel": "misc", "infomap_label_init_kernel": "misc",
+    "infomap_label_count_kernel": "misc", "infomap_label_head_kernel": "misc", "infomap_label_write_kernel": "misc",
     # rank_eval.hip
     "rank_eval_row_kernel": "misc", "rank_eval_reduce_kernel": "misc",
 }
