@@ -518,7 +518,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_vec_kernel(const float* __r
     }
 }
 
-// Split-K reduction of the weight gradient of a convolution whose frozen-statistics BatchNorm is folded into it (norm.hip, "conv +
+// Split-K reduction of the weight gradient of a convolution whose frozen-statistics BatchNorm is folded into it (norm_fold.hip, "conv +
 // frozen-statistics BatchNorm"): ONE workgroup per filter row k sums the slabs of its row (float4 columns, the summation tree of
 // splitk_reduce_vec_kernel: same G bit for bit), and finishes the fold while G is in registers — dgamma[k] = invstd (sum_m W G - mean
 // sum g), dbeta[k] = sum g (from the slice partials), dW = scale[k] G.  Replaces splitk_reduce_vec_kernel + bn_fold_wgrad_kernel:
@@ -621,7 +621,7 @@ extern "C" int rg_weights_to_krsc_multi(const void* table, int count, int total_
 
 extern "C" int rg_bn_fold_wgrad(const float* w, float* g, const float* scale, const float* invstd, const float* running_mean,
                                 const float* sum_g, const float* partials, int n_slices, float* dbeta, float* dgamma, int K,
-                                int M, hipStream_t stream);        // norm.hip
+                                int M, hipStream_t stream);        // norm_fold.hip
 
 // VEC / VECA of the loader (conv_wgrad_kernel) from vec / veca; the plane kernels (conv_planes.h) have 4 or 8 waves
 #define RG_WGRAD_LAUNCH_K(KERNEL, NTH, BM_, BN_, WM_, WN_)                                                          \

@@ -10,12 +10,7 @@
 
 namespace {
 
-static unsigned grid_for(int64_t items) {
-    int64_t g = rg::cdiv64(items, 256);
-    if (g > 4096) g = 4096;
-    if (g < 1) g = 1;
-    return (unsigned)g;
-}
+constexpr int64_t GRID_CAP = 4096;                     // workgroups of the grid-stride kernels (rg::grid_for)
 
 #define RG_GRID_STRIDE(i, n) \
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
@@ -237,7 +232,7 @@ extern "C" int rg_act_fwd(const float* x, float* y, int64_t n, int act, float sl
     RG_REQUIRE(x && y && n >= 0, "rg_act_fwd: bad arguments");
     if (n == 0) return RG_OK;
     rg::ProfScope prof(rg::FAM_ELTWISE, stream, 0.0, 8.0 * n);
-    hipLaunchKernelGGL(act_fwd_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, stream, x, y, n, act, slope);
+    hipLaunchKernelGGL(act_fwd_kernel, dim3(rg::grid_for(n / 4 + 1, GRID_CAP)), dim3(256), 0, stream, x, y, n, act, slope);
     return rg::check_launch("rg_act_fwd");
 }
 
@@ -246,7 +241,7 @@ extern "C" int rg_act_bwd(const float* dy, const float* y, float* dx, int64_t n,
     RG_REQUIRE(dy && y && dx && n >= 0, "rg_act_bwd: bad arguments");
     if (n == 0) return RG_OK;
     rg::ProfScope prof(rg::FAM_ELTWISE, stream, 0.0, 12.0 * n);
-    hipLaunchKernelGGL(act_bwd_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, stream, dy, y, dx, n, act, slope);
+    hipLaunchKernelGGL(act_bwd_kernel, dim3(rg::grid_for(n / 4 + 1, GRID_CAP)), dim3(256), 0, stream, dy, y, dx, n, act, slope);
     return rg::check_launch("rg_act_bwd");
 }
 
@@ -255,7 +250,7 @@ extern "C" int rg_axpby(const float* a, const float* b, float* y, int64_t n, flo
     RG_REQUIRE(a && y && n >= 0, "rg_axpby: bad arguments");
     if (n == 0) return RG_OK;
     rg::ProfScope prof(rg::FAM_ELTWISE, stream, 0.0, (b ? 12.0 : 8.0) * n);
-    hipLaunchKernelGGL(axpby_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, stream, a, b, y, n, alpha, beta);
+    hipLaunchKernelGGL(axpby_kernel, dim3(rg::grid_for(n / 4 + 1, GRID_CAP)), dim3(256), 0, stream, a, b, y, n, alpha, beta);
     return rg::check_launch("rg_axpby");
 }
 
@@ -291,7 +286,7 @@ extern "C" int rg_pair_cat(const float* a, const float* b, const int64_t* take_a
 extern "C" int rg_fill(float* y, int64_t n, float v, hipStream_t stream) {
     RG_REQUIRE(y && n >= 0, "rg_fill: bad arguments");
     if (n == 0) return RG_OK;
-    hipLaunchKernelGGL(fill_kernel, dim3(grid_for(n)), dim3(256), 0, stream, y, n, v);
+    hipLaunchKernelGGL(fill_kernel, dim3(rg::grid_for(n, GRID_CAP)), dim3(256), 0, stream, y, n, v);
     return rg::check_launch("rg_fill");
 }
 
@@ -318,7 +313,7 @@ extern "C" int rg_sub_square_fwd(const float* a, const float* b, float* y, int64
     RG_REQUIRE(a && b && y && n >= 0, "rg_sub_square_fwd: bad arguments");
     if (n == 0) return RG_OK;
     rg::ProfScope prof(rg::FAM_ELTWISE, stream, 0.0, 12.0 * n);
-    hipLaunchKernelGGL(sub_square_fwd_kernel, dim3(grid_for(n)), dim3(256), 0, stream, a, b, y, n);
+    hipLaunchKernelGGL(sub_square_fwd_kernel, dim3(rg::grid_for(n, GRID_CAP)), dim3(256), 0, stream, a, b, y, n);
     return rg::check_launch("rg_sub_square_fwd");
 }
 
@@ -327,7 +322,7 @@ extern "C" int rg_sub_square_bwd(const float* a, const float* b, const float* dy
     RG_REQUIRE(a && b && dy && (da || db) && n >= 0, "rg_sub_square_bwd: bad arguments");
     if (n == 0) return RG_OK;
     rg::ProfScope prof(rg::FAM_ELTWISE, stream, 0.0, 20.0 * n);
-    hipLaunchKernelGGL(sub_square_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, stream, a, b, dy, da, db, n);
+    hipLaunchKernelGGL(sub_square_bwd_kernel, dim3(rg::grid_for(n, GRID_CAP)), dim3(256), 0, stream, a, b, dy, da, db, n);
     return rg::check_launch("rg_sub_square_bwd");
 }
 
@@ -335,7 +330,7 @@ extern "C" int rg_dropout(const float* x, float* y, int64_t n, float p, unsigned
     RG_REQUIRE(x && y && n >= 0 && p >= 0.f && p < 1.f, "rg_dropout: bad arguments");
     if (n == 0) return RG_OK;
     rg::ProfScope prof(rg::FAM_ELTWISE, stream, 0.0, 8.0 * n);
-    hipLaunchKernelGGL(dropout_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, y, n, p, seed, (const unsigned long long*)nullptr);
+    hipLaunchKernelGGL(dropout_kernel, dim3(rg::grid_for(n, GRID_CAP)), dim3(256), 0, stream, x, y, n, p, seed, (const unsigned long long*)nullptr);
     return rg::check_launch("rg_dropout");
 }
 
@@ -346,7 +341,7 @@ extern "C" int rg_dropout_clocked(const float* x, float* y, int64_t n, float p, 
     RG_REQUIRE(x && y && clock && n >= 0 && p >= 0.f && p < 1.f, "rg_dropout_clocked: bad arguments");
     if (n == 0) return RG_OK;
     rg::ProfScope prof(rg::FAM_ELTWISE, stream, 0.0, 8.0 * n);
-    hipLaunchKernelGGL(dropout_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, y, n, p, seed, clock);
+    hipLaunchKernelGGL(dropout_kernel, dim3(rg::grid_for(n, GRID_CAP)), dim3(256), 0, stream, x, y, n, p, seed, clock);
     return rg::check_launch("rg_dropout_clocked");
 }
 
@@ -393,7 +388,7 @@ extern "C" int rg_copy_channels(const float* src, float* dst, int N, int Cc, int
     RG_REQUIRE(sc0 >= 0 && sc0 + Cc <= Cs && dc0 >= 0 && dc0 + Cc <= Cd, "rg_copy_channels: channel range out of bounds");
     const int64_t total = (int64_t)N * Cc * HW;
     rg::ProfScope prof(rg::FAM_ELTWISE, stream, 0.0, 8.0 * total);
-    hipLaunchKernelGGL(copy_channels_kernel, dim3(grid_for(total)), dim3(256), 0, stream, src, dst, total, Cc, HW, Cs,
+    hipLaunchKernelGGL(copy_channels_kernel, dim3(rg::grid_for(total, GRID_CAP)), dim3(256), 0, stream, src, dst, total, Cc, HW, Cs,
                        sc0, Cd, dc0, accumulate);
     return rg::check_launch("rg_copy_channels");
 }
@@ -430,7 +425,7 @@ extern "C" int rg_mix_rows_fwd(const float* src, const void* idx_a, const void* 
     RG_REQUIRE(src && idx_a && idx_b && out && rows_src > 0 && rows_out > 0 && len > 0, "rg_mix_rows_fwd: bad arguments");
     const int64_t total = (int64_t)rows_out * len;
     rg::ProfScope prof(rg::FAM_ELTWISE, stream, 0.0, 12.0 * total);
-    hipLaunchKernelGGL(mix_rows_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, stream, src,
+    hipLaunchKernelGGL(mix_rows_fwd_kernel, dim3(rg::grid_for(total, GRID_CAP)), dim3(256), 0, stream, src,
                        static_cast<const long long*>(idx_a), static_cast<const long long*>(idx_b), lam, out, len, total);
     return rg::check_launch("rg_mix_rows_fwd");
 }
@@ -440,7 +435,7 @@ extern "C" int rg_mix_rows_bwd(const float* g, const void* idx_a, const void* id
     RG_REQUIRE(g && idx_a && idx_b && dsrc && rows_src > 0 && rows_out > 0 && len > 0, "rg_mix_rows_bwd: bad arguments");
     const int64_t total = (int64_t)rows_src * len;
     rg::ProfScope prof(rg::FAM_ELTWISE, stream, 0.0, 4.0 * total * (1.0 + rows_out));
-    hipLaunchKernelGGL(mix_rows_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, stream, g,
+    hipLaunchKernelGGL(mix_rows_bwd_kernel, dim3(rg::grid_for(total, GRID_CAP)), dim3(256), 0, stream, g,
                        static_cast<const long long*>(idx_a), static_cast<const long long*>(idx_b), lam, dsrc, rows_out, len,
                        total);
     return rg::check_launch("rg_mix_rows_bwd");

@@ -6,12 +6,7 @@
 
 namespace {
 
-static unsigned grid_for(int64_t items) {
-    int64_t g = rg::cdiv64(items, 256);
-    if (g > 8192) g = 8192;
-    if (g < 1) g = 1;
-    return (unsigned)g;
-}
+constexpr int64_t GRID_CAP = 8192;                     // workgroups of the grid-stride kernels (rg::grid_for)
 
 #define RG_GRID_STRIDE(i, n) \
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
@@ -341,7 +336,7 @@ extern "C" int rg_avgpool2d_fwd(const float* x, float* y, int N, int C, int H, i
     const int P = H / k, Q = W / k;
     const int64_t total = (int64_t)N * C * P * Q;
     rg::ProfScope prof(rg::FAM_POOL, stream, 0.0, 4.0 * (total + (double)N * C * H * W));
-    hipLaunchKernelGGL(avgpool_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, stream, x, y, H, W, k, P, Q, total);
+    hipLaunchKernelGGL(avgpool_fwd_kernel, dim3(rg::grid_for(total, GRID_CAP)), dim3(256), 0, stream, x, y, H, W, k, P, Q, total);
     return rg::check_launch("rg_avgpool2d_fwd");
 }
 
@@ -350,7 +345,7 @@ extern "C" int rg_avgpool2d_bwd(const float* dy, float* dx, int N, int C, int H,
     const int P = H / k, Q = W / k;
     const int64_t total = (int64_t)N * C * H * W;
     rg::ProfScope prof(rg::FAM_POOL, stream, 0.0, 4.0 * (total + (double)N * C * P * Q));
-    hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, stream, dy, dx, H, W, k, P, Q, total);
+    hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(rg::grid_for(total, GRID_CAP)), dim3(256), 0, stream, dy, dx, H, W, k, P, Q, total);
     return rg::check_launch("rg_avgpool2d_bwd");
 }
 
@@ -367,12 +362,12 @@ extern "C" int rg_reflection_pad2d_fwd(const float* x, float* y, int N, int C, i
     const bool vec = (W & 3) == 0 && pad <= 3 && W >= 8 && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
     if (vec) {
         const int64_t total4 = (int64_t)N * C * H * (W >> 2);
-        hipLaunchKernelGGL(reflect_pad_fwd_vec_kernel, dim3(grid_for(total4)), dim3(256), 0, stream, x, y, H, W, pad, OH, OW, (int)total4,
+        hipLaunchKernelGGL(reflect_pad_fwd_vec_kernel, dim3(rg::grid_for(total4, GRID_CAP)), dim3(256), 0, stream, x, y, H, W, pad, OH, OW, (int)total4,
                            make_paddiv(W >> 2), make_paddiv(H), act, slope, (unsigned)(total * 4));
         return rg::check_launch("rg_reflection_pad2d_fwd");
     }
     RG_REQUIRE(act == RG_ACT_NONE, "rg_reflection_pad2d_fwd: the fused activation needs W %% 4 == 0, W >= 8 and pad <= 3");
-    hipLaunchKernelGGL(reflect_pad_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, stream, x, y, H, W, pad, OH, OW, (int)total,
+    hipLaunchKernelGGL(reflect_pad_fwd_kernel, dim3(rg::grid_for(total, GRID_CAP)), dim3(256), 0, stream, x, y, H, W, pad, OH, OW, (int)total,
                        make_paddiv(OW), make_paddiv(OH));
     return rg::check_launch("rg_reflection_pad2d_fwd");
 }
@@ -390,12 +385,12 @@ extern "C" int rg_reflection_pad2d_bwd(const float* dy, const float* x_act, floa
     const bool vec = (W & 3) == 0 && pad <= 3 && W >= 8 && (((reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(x_act)) & 15) == 0);
     if (vec) {
         const int64_t total4 = total >> 2;
-        hipLaunchKernelGGL(reflect_pad_bwd_vec_kernel, dim3(grid_for(total4)), dim3(256), 0, stream, dy, x_act, dx, H, W, pad, OH, OW,
+        hipLaunchKernelGGL(reflect_pad_bwd_vec_kernel, dim3(rg::grid_for(total4, GRID_CAP)), dim3(256), 0, stream, dy, x_act, dx, H, W, pad, OH, OW,
                            (int)total4, make_paddiv(W >> 2), make_paddiv(H), act, slope, (unsigned)((int64_t)N * C * OH * OW * 4));
         return rg::check_launch("rg_reflection_pad2d_bwd");
     }
     RG_REQUIRE(act == RG_ACT_NONE, "rg_reflection_pad2d_bwd: the fused activation needs W %% 4 == 0, W >= 8 and pad <= 3");
-    hipLaunchKernelGGL(reflect_pad_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, stream, dy, dx, H, W, pad, OH, OW, (int)total,
+    hipLaunchKernelGGL(reflect_pad_bwd_kernel, dim3(rg::grid_for(total, GRID_CAP)), dim3(256), 0, stream, dy, dx, H, W, pad, OH, OW, (int)total,
                        make_paddiv(W), make_paddiv(H));
     return rg::check_launch("rg_reflection_pad2d_bwd");
 }
@@ -409,7 +404,7 @@ extern "C" int rg_spectral_norm_fwd(const float* w, float* u, float* v, float* w
     hipLaunchKernelGGL(spectral_norm_power_kernel, dim3(1), dim3(SN_THREADS), 0, stream, w, u, v, sigma, uv_saved, K, M, training,
                        eps);
     const int64_t n = (int64_t)K * M;
-    hipLaunchKernelGGL(scale_by_device_scalar_kernel, dim3(grid_for(n)), dim3(256), 0, stream, w, w_sn, sigma + 1, n);
+    hipLaunchKernelGGL(scale_by_device_scalar_kernel, dim3(rg::grid_for(n, GRID_CAP)), dim3(256), 0, stream, w, w_sn, sigma + 1, n);
     return rg::check_launch("rg_spectral_norm_fwd");
 }
 
@@ -494,7 +489,7 @@ extern "C" int rg_spectral_norm_bwd(const float* dw_sn, const float* w_sn, const
         }
         float* part = static_cast<float*>(workspace);
         hipLaunchKernelGGL(spectral_norm_dot_partial_kernel, dim3(SN_SLICES), dim3(256), 0, stream, dw_sn, w_sn, part, n);
-        hipLaunchKernelGGL(spectral_norm_bwd_apply_kernel, dim3(grid_for(n)), dim3(256), 0, stream, dw_sn, part, u, v, sigma, dw,
+        hipLaunchKernelGGL(spectral_norm_bwd_apply_kernel, dim3(rg::grid_for(n, GRID_CAP)), dim3(256), 0, stream, dw_sn, part, u, v, sigma, dw,
                            K, M, accumulate);
         return rg::check_launch("rg_spectral_norm_bwd");
     }

@@ -257,12 +257,7 @@ __global__ void wsum_bwd_kernel(const float* __restrict__ gout, const float* __r
         dx[i] = w ? g * w[i] : g;
 }
 
-static unsigned grid_for(int64_t items) {
-    int64_t g = rg::cdiv64(items, 256);
-    if (g > 4096) g = 4096;
-    if (g < 1) g = 1;
-    return (unsigned)g;
-}
+constexpr int64_t GRID_CAP = 4096;                     // workgroups of the grid-stride kernels (rg::grid_for)
 
 
 // WGAN-GP penalty rows, CC/dual_gan/models/external_function.py:100-101: per sample r with g = grads[r] + 1e-16,
@@ -310,7 +305,7 @@ extern "C" int rg_sigmoid_bce_bwd(const float* x, const float* grad_out, float* 
                                   float grad_scale, hipStream_t stream) {
     RG_REQUIRE(x && dx && n > 0, "rg_sigmoid_bce_bwd: bad arguments");
     rg::ProfScope prof(rg::FAM_LOSS, stream, 0.0, 8.0 * n);
-    hipLaunchKernelGGL(bce_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, grad_out, dx, n, target,
+    hipLaunchKernelGGL(bce_bwd_kernel, dim3(rg::grid_for(n, GRID_CAP)), dim3(256), 0, stream, x, grad_out, dx, n, target,
                        grad_scale / (float)n);
     return rg::check_launch("rg_sigmoid_bce_bwd");
 }
@@ -331,7 +326,7 @@ extern "C" int rg_mse_const_bwd(const float* x, const float* grad_out, float* dx
                                 float grad_scale, hipStream_t stream) {
     RG_REQUIRE(x && dx && n > 0, "rg_mse_const_bwd: bad arguments");
     rg::ProfScope prof(rg::FAM_LOSS, stream, 0.0, 8.0 * n);
-    hipLaunchKernelGGL(mse_const_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, grad_out, dx, n, target,
+    hipLaunchKernelGGL(mse_const_bwd_kernel, dim3(rg::grid_for(n, GRID_CAP)), dim3(256), 0, stream, x, grad_out, dx, n, target,
                        grad_scale / (float)n);
     return rg::check_launch("rg_mse_const_bwd");
 }
@@ -352,7 +347,7 @@ extern "C" int rg_affine_relu_mean_bwd(const float* x, const float* grad_out, fl
                                        int clamp, float grad_scale, hipStream_t stream) {
     RG_REQUIRE(x && dx && n > 0, "rg_affine_relu_mean_bwd: bad arguments");
     rg::ProfScope prof(rg::FAM_LOSS, stream, 0.0, 8.0 * n);
-    hipLaunchKernelGGL(affine_relu_mean_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, grad_out, dx, n, a, b, clamp,
+    hipLaunchKernelGGL(affine_relu_mean_bwd_kernel, dim3(rg::grid_for(n, GRID_CAP)), dim3(256), 0, stream, x, grad_out, dx, n, a, b, clamp,
                        grad_scale / (float)n);
     return rg::check_launch("rg_affine_relu_mean_bwd");
 }
@@ -377,7 +372,7 @@ extern "C" int rg_l1_bwd(const float* a, const float* b, const int64_t* row_labe
     RG_REQUIRE(a && b && out2 && (da || db) && rows > 0 && inner > 0, "rg_l1_bwd: bad arguments");
     const int64_t n = (int64_t)rows * inner;
     rg::ProfScope prof(rg::FAM_LOSS, stream, 0.0, 16.0 * n);
-    hipLaunchKernelGGL(l1_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, stream, a, b, row_labels, grad_out, out2 + 1, da,
+    hipLaunchKernelGGL(l1_bwd_kernel, dim3(rg::grid_for(n, GRID_CAP)), dim3(256), 0, stream, a, b, row_labels, grad_out, out2 + 1, da,
                        db, n, inner, grad_scale);
     return rg::check_launch("rg_l1_bwd");
 }
@@ -394,7 +389,7 @@ extern "C" int rg_l1_rows_bwd(const float* a, const float* b, const float* grad_
     RG_REQUIRE(a && b && grad_rows && (da || db) && rows > 0 && inner > 0, "rg_l1_rows_bwd: bad arguments");
     const int64_t n = (int64_t)rows * inner;
     rg::ProfScope prof(rg::FAM_LOSS, stream, 0.0, 16.0 * n);
-    hipLaunchKernelGGL(l1_rows_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, stream, a, b, grad_rows, da, db, n, inner);
+    hipLaunchKernelGGL(l1_rows_bwd_kernel, dim3(rg::grid_for(n, GRID_CAP)), dim3(256), 0, stream, a, b, grad_rows, da, db, n, inner);
     return rg::check_launch("rg_l1_rows_bwd");
 }
 
@@ -410,7 +405,7 @@ extern "C" int rg_mse_const_rows_bwd(const float* x, float c, const float* grad_
     RG_REQUIRE(x && grad_rows && dx && rows > 0 && inner > 0, "rg_mse_const_rows_bwd: bad arguments");
     const int64_t n = (int64_t)rows * inner;
     rg::ProfScope prof(rg::FAM_LOSS, stream, 0.0, 8.0 * n);
-    hipLaunchKernelGGL(mse_const_rows_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, c, grad_rows, dx, n, inner);
+    hipLaunchKernelGGL(mse_const_rows_bwd_kernel, dim3(rg::grid_for(n, GRID_CAP)), dim3(256), 0, stream, x, c, grad_rows, dx, n, inner);
     return rg::check_launch("rg_mse_const_rows_bwd");
 }
 
@@ -441,7 +436,7 @@ extern "C" int rg_weighted_sum_fwd(const float* x, const float* w, float* out, i
 extern "C" int rg_weighted_sum_bwd(const float* grad_out, const float* w, float* dx, int64_t n, float scale,
                                    hipStream_t stream) {
     RG_REQUIRE(dx && n > 0, "rg_weighted_sum_bwd: bad arguments");
-    hipLaunchKernelGGL(wsum_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, stream, grad_out, w, dx, n, scale);
+    hipLaunchKernelGGL(wsum_bwd_kernel, dim3(rg::grid_for(n, GRID_CAP)), dim3(256), 0, stream, grad_out, w, dx, n, scale);
     return rg::check_launch("rg_weighted_sum_bwd");
 }
 

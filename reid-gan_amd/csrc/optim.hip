@@ -9,12 +9,7 @@
 
 namespace {
 
-static unsigned grid_for(int64_t items) {
-    int64_t g = rg::cdiv64(items, 256);
-    if (g > 8192) g = 8192;
-    if (g < 1) g = 1;
-    return (unsigned)g;
-}
+constexpr int64_t GRID_CAP = 8192;                     // workgroups of the grid-stride kernels (rg::grid_for)
 
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, int64_t n, float lr, float beta1, float beta2, float eps, float wd,
@@ -106,7 +101,7 @@ extern "C" int rg_adam_step(float* p, const float* g, float* exp_avg, float* exp
     const double bc1 = 1.0 - pow((double)beta1, step);
     const double bc2 = 1.0 - pow((double)beta2, step);
     rg::ProfScope prof(rg::FAM_OPTIM, stream, 0.0, 28.0 * n);
-    hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, stream, p, g, exp_avg, exp_avg_sq, n, lr,
+    hipLaunchKernelGGL(adam_kernel, dim3(rg::grid_for(n / 4 + 1, GRID_CAP)), dim3(256), 0, stream, p, g, exp_avg, exp_avg_sq, n, lr,
                        beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), grad_scale);
     return rg::check_launch("rg_adam_step");
 }
@@ -115,7 +110,7 @@ extern "C" int rg_sgd_step(float* p, const float* g, float* momentum_buf, int64_
                            float weight_decay, int first_step, float grad_scale, hipStream_t stream) {
     RG_REQUIRE(p && g && n > 0 && (momentum == 0.f || momentum_buf), "rg_sgd_step: bad arguments");
     rg::ProfScope prof(rg::FAM_OPTIM, stream, 0.0, 20.0 * n);
-    hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(n)), dim3(256), 0, stream, p, g, momentum_buf, n, lr, momentum,
+    hipLaunchKernelGGL(sgd_kernel, dim3(rg::grid_for(n, GRID_CAP)), dim3(256), 0, stream, p, g, momentum_buf, n, lr, momentum,
                        weight_decay, first_step, grad_scale);
     return rg::check_launch("rg_sgd_step");
 }
@@ -133,7 +128,7 @@ extern "C" int rg_adam_step_dev(float* p, const float* g, float* exp_avg, float*
                                 hipStream_t stream) {
     RG_REQUIRE(p && g && exp_avg && exp_avg_sq && state && n > 0, "rg_adam_step_dev: bad arguments");
     rg::ProfScope prof(rg::FAM_OPTIM, stream, 0.0, 28.0 * n);
-    hipLaunchKernelGGL(adam_dev_kernel, dim3(grid_for(n)), dim3(256), 0, stream, p, g, exp_avg, exp_avg_sq, n, lr, beta1, beta2,
+    hipLaunchKernelGGL(adam_dev_kernel, dim3(rg::grid_for(n, GRID_CAP)), dim3(256), 0, stream, p, g, exp_avg, exp_avg_sq, n, lr, beta1, beta2,
                        eps, weight_decay, state, grad_scale);
     return rg::check_launch("rg_adam_step_dev");
 }

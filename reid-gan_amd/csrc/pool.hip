@@ -6,12 +6,7 @@
 
 namespace {
 
-static unsigned grid_for(int64_t items) {
-    int64_t g = rg::cdiv64(items, 256);
-    if (g > 8192) g = 8192;
-    if (g < 1) g = 1;
-    return (unsigned)g;
-}
+constexpr int64_t GRID_CAP = 8192;                     // workgroups of the grid-stride kernels (rg::grid_for)
 
 // y[n,c,p,q] = max over the window; arg = window-local index (r*KW+s) of the FIRST maximum in scan
 // order (torch semantics), NaN propagates like torch (a NaN wins).
@@ -310,7 +305,7 @@ extern "C" int rg_maxpool2d_fwd(const float* x, float* y, unsigned char* argmax,
     RG_REQUIRE(KH * KW <= 255 && PH < KH && PW < KW, "rg_maxpool2d_fwd: unsupported window");
     const int64_t total = (int64_t)N * C * P * Q;
     rg::ProfScope prof(rg::FAM_POOL, stream, 0.0, 4.0 * N * C * ((double)H * W + 1.25 * P * Q));
-    hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, stream, x, y, argmax, total, H, W, P, Q,
+    hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(rg::grid_for(total, GRID_CAP)), dim3(256), 0, stream, x, y, argmax, total, H, W, P, Q,
                        KH, KW, SH, SW, PH, PW);
     return rg::check_launch("rg_maxpool2d_fwd");
 }
@@ -351,7 +346,7 @@ extern "C" int rg_global_avgpool_bwd(const float* dy, float* dx, int N, int C, i
     RG_REQUIRE(dy && dx && N > 0 && C > 0 && HW > 0, "rg_global_avgpool_bwd: bad arguments");
     const int64_t total = (int64_t)N * C * HW;
     rg::ProfScope prof(rg::FAM_POOL, stream, 0.0, 4.0 * total);
-    hipLaunchKernelGGL(gap_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, stream, dy, dx, total, HW);
+    hipLaunchKernelGGL(gap_bwd_kernel, dim3(rg::grid_for(total, GRID_CAP)), dim3(256), 0, stream, dy, dx, total, HW);
     return rg::check_launch("rg_global_avgpool_bwd");
 }
 

@@ -120,12 +120,7 @@ __global__ __launch_bounds__(256) void bicubic_norm_bwd_kernel(const float* __re
     }
 }
 
-static unsigned grid_for(int64_t items) {
-    int64_t g = rg::cdiv64(items, 256);
-    if (g > 8192) g = 8192;
-    if (g < 1) g = 1;
-    return (unsigned)g;
-}
+constexpr int64_t GRID_CAP = 8192;                     // workgroups of the grid-stride kernels (rg::grid_for)
 
 }  // namespace
 
@@ -135,7 +130,7 @@ extern "C" int rg_bicubic_normalize_fwd(const float* x, float* y, int N, int C, 
     RG_REQUIRE((mean == nullptr) == (stdv == nullptr), "rg_bicubic_normalize_fwd: mean and std go together");
     const int64_t total = (int64_t)N * C * OH * OW;
     rg::ProfScope prof(rg::FAM_ELTWISE, stream, 0.0, 4.0 * (total + (double)N * C * H * W));
-    hipLaunchKernelGGL(bicubic_norm_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, stream, x, y, C, H, W, OH, OW,
+    hipLaunchKernelGGL(bicubic_norm_fwd_kernel, dim3(rg::grid_for(total, GRID_CAP)), dim3(256), 0, stream, x, y, C, H, W, OH, OW,
                        (float)H / (float)OH, (float)W / (float)OW, mean, stdv, total);
     return rg::check_launch("rg_bicubic_normalize_fwd");
 }
@@ -145,7 +140,7 @@ extern "C" int rg_bicubic_normalize_bwd(const float* dy, float* dx, int N, int C
     RG_REQUIRE(dy && dx && N > 0 && C > 0 && H > 0 && W > 0 && OH > 0 && OW > 0, "rg_bicubic_normalize_bwd: bad arguments");
     const int64_t total = (int64_t)N * C * H * W;
     rg::ProfScope prof(rg::FAM_ELTWISE, stream, 0.0, 4.0 * (total + (double)N * C * OH * OW));
-    hipLaunchKernelGGL(bicubic_norm_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, stream, dy, dx, C, H, W, OH, OW,
+    hipLaunchKernelGGL(bicubic_norm_bwd_kernel, dim3(rg::grid_for(total, GRID_CAP)), dim3(256), 0, stream, dy, dx, C, H, W, OH, OW,
                        (float)H / (float)OH, (float)W / (float)OW, (float)OH / (float)H, (float)OW / (float)W, stdv,
                        total);
     return rg::check_launch("rg_bicubic_normalize_bwd");

@@ -64,6 +64,14 @@ struct ProfScope {
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// workgroups of 256 threads for a grid-stride kernel over `items`, between 1 and the unit's cap
+static inline unsigned grid_for(int64_t items, int64_t cap) {
+    int64_t g = cdiv64(items, 256);
+    if (g > cap) g = cap;
+    if (g < 1) g = 1;
+    return (unsigned)g;
+}
+
 // integer switch from the environment (README "Environment switches"); callers read each one once per process
 static inline int env_int(const char* name, int dflt) {
     const char* e = getenv(name);

@@ -490,7 +490,7 @@ class _BatchNorm(RGModule):
 # ---- convolution + BatchNorm as one layer ------------------------------------------------------------------------
 # With running statistics (FD-GAN's E and D_id: `set_bn_fix`, every eval-mode network) the normalisation is a per-channel
 # affine map of the conv output: it runs in the conv epilogue together with the residual add and the ReLU, and the
-# pre-normalisation tensor is never written or read again (see csrc/norm.hip, "conv + frozen-statistics BatchNorm").
+# pre-normalisation tensor is never written or read again (see csrc/norm_fold.hip, "conv + frozen-statistics BatchNorm").
 # Train-mode BatchNorm keeps the separate statistics / apply passes.
 class _Fold(object):
     __slots__ = ("key", "scale", "shift", "invstd", "w_scaled", "w_scaled_krsc")

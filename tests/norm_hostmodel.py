@@ -1,4 +1,4 @@
-"""Host model of the normalisation unit (csrc/norm.hip without the IBN layer) — the comparison partner of
+"""Host model of the normalisation units csrc/norm_bn.hip, norm_instnorm.hip and norm_fold.hip — the comparison partner of
 tests/test_norm_elementwise_gpu.py, tied to float32 torch by tests/test_norm_hostmodel_cpu.py.  No tests and no GPU here.
 
 Three parts:

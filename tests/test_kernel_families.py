@@ -1,5 +1,5 @@
 """Every __global__ kernel of reid-gan_amd/csrc/*.hip has a row in tools/kernel_families.py (the table behind the per-family HBM
-traffic of `roofline.traffic`), so a new kernel cannot silently be booked under "other"."""
+traffic of `roofline.traffic`), so a new kernel cannot silently be booked under "other"; and every row is a kernel of the sources."""
 import os
 import sys
 
@@ -13,6 +13,13 @@ def test_every_source_kernel_has_a_family():
     assert len(src) > 90
     missing = sorted(k for k in src if k not in KF.FAMILY)
     assert not missing, "kernels without a family row in tools/kernel_families.py: %s" % missing
+
+
+def test_every_family_row_is_a_source_kernel():
+    import kernel_families as KF
+    src = KF.source_kernels(os.path.join(ROOT, "reid-gan_amd", "csrc"))
+    stale = sorted(k for k in KF.FAMILY if k not in src)
+    assert not stale, "rows of tools/kernel_families.py whose kernel is in no source: %s" % stale
 
 
 def test_rocprof_names_resolve():

@@ -1,4 +1,4 @@
-"""GPU: every entry point of csrc/norm.hip except the IBN layer, per element against the fp64 host model
+"""GPU: every entry point of csrc/norm_bn.hip, norm_instnorm.hip and norm_fold.hip, per element against the fp64 host model
 (tests/norm_hostmodel.py) with its per-element error budgets, at geometries built from the dispatch arithmetic: every value of
 bn_reg_units and every reachable (LANES, U) of InstanceNorm with a full and a ragged geometry, the scalar and the loop routes,
 every pick_slices regime — with the optional arguments given and NULL, the input families plain / scales / offset / constant /

@@ -5,7 +5,8 @@ of the rg::ProfScope the kernel is launched under (rg_common.h `enum Family`), e
 finish or feed a convolution launch — split-K finishers, the folded-BatchNorm weight-gradient finisher, filter re-layouts /
 folds, fp8 quantisation — are booked on the convolution family they serve, because `roofline.traffic` is "HBM bytes the conv
 family moves per launch, everything it needs included".  tests/test_kernel_families.py fails when a kernel of the sources is
-missing here, so a new kernel cannot silently land in "other" (round 2: conv3x3_halo / bn_fold_wgrad / *_k1 / smallc did).
+missing here, so a new kernel cannot silently land in "other" (round 2: conv3x3_halo / bn_fold_wgrad / *_k1 / smallc did), and
+when a row names a kernel the sources no longer have.
 """
 
 CONV = "conv"            # fp32 implicit-GEMM family (FAM_CONV_FWD / _DGRAD / _WGRAD + its helpers)
@@ -23,21 +24,24 @@ FAMILY = {
     # conv_halo.h, conv_finish.h, conv_planes.h (instantiated by the units above)
     "conv3x3_halo_kernel": CONV, "conv_splitk_finish_kernel": CONV, "conv_splitk_finish_vec_kernel": CONV,
     "conv_fwd_pl_kernel": CONV, "conv_dgrad_pl_kernel": CONV, "conv_wgrad_pl_kernel": CONV,
-    # norm.hip: conv helpers of the folded (frozen-statistics) BatchNorm
+    # norm_fold.hip: conv helpers of the folded (frozen-statistics) BatchNorm
     "bn_fold_wgrad_kernel": CONV, "fold_filters_multi_kernel": CONV, "bn_fold_kernel": CONV,
     # conv_f8.hip
     "conv_f8_kernel": CONV_F8, "f8_amax_kernel": CONV_F8, "f8_quantize_dual_kernel": CONV_F8,
     "f8_quantize_transpose_kernel": CONV_F8, "f8_roll_kernel": CONV_F8, "f8_splitk_reduce_kernel": CONV_F8, "f8_splitk_reduce_vec_kernel": CONV_F8,
-    # norm.hip
-    "act_bwd_sum_kernel": "norm", "bn_apply_fwd_kernel": "norm", "bn_bwd_apply_kernel": "norm",
+    # norm_bn.h (instantiated by norm_bn.hip and norm_dsbn.hip), norm_bn.hip
+    "bn_apply_fwd_kernel": "norm", "bn_bwd_apply_kernel": "norm",
     "bn_bwd_reduce_finalize_kernel": "norm", "bn_bwd_reduce_partial_kernel": "norm", "bn_eval_bwd_fused_kernel": "norm",
     "bn_stats_finalize_kernel": "norm", "bn_stats_partial_kernel": "norm", "bn_train_bwd_fused_kernel": "norm",
-    "bn_train_fwd_fused_kernel": "norm", "instnorm_bwd_kernel": "norm", "instnorm_fwd_kernel": "norm",
-    "bn_train_fwd_reg_kernel": "norm", "channel_sum_small_kernel": "norm", "bn_train_bwd_reg_kernel": "norm", "instnorm_fwd_reg_kernel": "norm", "instnorm_bwd_reg_kernel": "norm",
-    "rows_sum_pair_kernel": "norm", "scale_rows_kernel": "norm", "sum_slices_kernel": "norm",
-    "bn_stats_from_partials_kernel": "norm", "bn_bwd_from_partials_kernel": "norm",
+    "bn_train_fwd_fused_kernel": "norm", "bn_train_fwd_reg_kernel": "norm", "bn_train_bwd_reg_kernel": "norm",
+    # norm_instnorm.hip
+    "instnorm_bwd_kernel": "norm", "instnorm_fwd_kernel": "norm", "instnorm_fwd_reg_kernel": "norm", "instnorm_bwd_reg_kernel": "norm",
+    # norm_ibn.hip
     "ibn_fwd_rows_kernel": "norm", "ibn_train_fwd_fused_kernel": "norm", "ibn_bwd_rows_kernel": "norm",
     "ibn_train_bwd_fused_kernel": "norm",
+    # norm_fold.hip: the generic sums
+    "act_bwd_sum_kernel": "norm", "channel_sum_small_kernel": "norm", "rows_sum_pair_kernel": "norm", "scale_rows_kernel": "norm",
+    "sum_slices_kernel": "norm",
     # part_head.hip
     "mp_head_col_fwd_kernel": "norm", "mp_head_row_fwd_kernel": "norm", "mp_head_eval_fwd_kernel": "norm",
     "mp_head_row_bwd_kernel": "norm", "mp_head_col_bwd_kernel": "norm",
@@ -63,7 +67,6 @@ FAMILY = {
     "cm_update_hard_kernel": "cm", "cm_update_kernel": "cm", "normalize_listed_rows_kernel": "cm",
     # bgemm.hip (attention), gan_extra.hip, resize.hip, retrieval.hip, datagen.hip: rg::FAM_MISC
     "bgemm_kernel": "misc", "softmax_rows_bwd_kernel": "misc", "softmax_rows_fwd_kernel": "misc",
-    "attn_fwd_kernel": "misc", "attn_bwd_kernel": "misc",
     "avgpool_bwd_kernel": "misc", "avgpool_fwd_kernel": "misc", "reflect_pad_bwd_kernel": "misc",
     "reflect_pad_fwd_kernel": "misc", "reflect_pad_fwd_vec_kernel": "misc", "reflect_pad_bwd_vec_kernel": "misc", "scale_by_device_scalar_kernel": "misc", "spectral_norm_bwd_apply_kernel": "misc",
     "spectral_norm_bwd_kernel": "misc", "spectral_norm_dot_partial_kernel": "misc", "spectral_norm_power_kernel": "misc",
