@@ -755,7 +755,7 @@ int dgrad_impl(const ConvGeom& g, const DgradOps& o, const Workspace& ws, hipStr
         else if (g.K % 16 == 0) c.mode = 1;
         if (c.mode) p.w = wk;
     }
-    // (a planning call has no pointers: rg_hip.ops always passes the [K][9][C] copy for such layers)
+    // (a planning call has no pointers: rg_hip/ops/conv.py always passes the [K][9][C] copy for such layers)
     if (allow_halo && dgrad_halo_geom(g) && (dry || dgrad_halo_operands(o.dy, wk))) {
         const HaloPlan hpl = halo_plan(p.M, c.s.ng_max, g.K, &c.ws);
         const int cols = hpl.splits > 1 ? 0 : hpl.n_tiles * 2;

@@ -8,7 +8,7 @@
 //             probability 1) to an L1 change <= 1e-13, then link flow p_i w_ij / w_i normalised and node flow = in-flow;
 //   L         plogp(sum enter) - sum plogp(enter) - sum plogp(exit) + sum plogp(exit + p) - sum_nodes plogp(p_node);
 //   search    synchronous local-move sweeps over units (leaves, then aggregated modules), at most one admitted move per module
-//             and sweep, driven from the host (rg_hip/ops.py: infomap_search).
+//             and sweep, driven from the host (rg_hip/ops/infomap.py: infomap_search).
 // Everything works on CSR lists.  All flow and codelength arithmetic is fp64 and every sum runs in a fixed order (a thread
 // walks its list front to back, a workgroup reduces in a fixed tree); the only atomics are integer ones whose result does
 // not depend on the order they land in, so two runs give the same bits.  No kernel waits on another workgroup and every

@@ -20,7 +20,7 @@ import torch
 
 from . import ops
 from .lib import lib
-from .ops import _chk, _p, _pair, _stream, workspace
+from .ops._base import _chk, _p, _pair, _stream, workspace
 from .wcache import Stamp
 
 E4M3, E5M2 = 0, 1

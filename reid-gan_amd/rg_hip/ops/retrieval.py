@@ -1,0 +1,247 @@
+"""Cluster memory, kNN and row helpers of the pseudo-labelling code, k-reciprocal re-ranking, CMC / mAP scoring:
+csrc/cm.hip, csrc/retrieval.hip, csrc/rerank.hip, csrc/rank_eval.hip."""
+from __future__ import absolute_import
+
+import torch
+
+from ._base import _chk, _chk_rr, _p, _stream, lib
+
+
+# ------------------------------------------------------------------------------------------------
+# cluster memory
+# ------------------------------------------------------------------------------------------------
+def cm_update(inputs, targets, features, momentum, hard=False, normalize_eps=False):
+    inputs = _chk(inputs, "inputs")
+    targets = _chk(targets, "targets", torch.int64)
+    if not (features.is_cuda and features.is_contiguous() and features.dtype == torch.float32):
+        raise RuntimeError("cm_update: the memory bank must be a contiguous fp32 GPU tensor (updated in place)")
+    B, D = inputs.shape
+    K = features.shape[0]
+    if hard:
+        lib.rg_cm_update_hard(_p(inputs), _p(targets), _p(features), B, D, K, float(momentum), _stream())
+    else:
+        lib.rg_cm_update(_p(inputs), _p(targets), _p(features), B, D, K, float(momentum), int(normalize_eps), _stream())
+    return features
+
+
+# ------------------------------------------------------------------------------------------------
+# row helpers of the pseudo-labelling front half: kNN, distances, cluster centres (csrc/cm.hip, csrc/retrieval.hip)
+# ------------------------------------------------------------------------------------------------
+def normalize_listed_rows(g, ids, eps=1e-16):
+    """in place: g[id] /= |g[id]| + eps for the listed (int64, device) row ids"""
+    g = _chk(g, "g")
+    ids = _chk(ids, "ids", torch.int64)
+    lib.rg_normalize_listed_rows(_p(g), _p(ids), ids.numel(), g.shape[0], g.shape[1], eps, _stream())
+    return g
+
+
+def topk_rows(s, k):
+    """(idx int32 [rows, k], val [rows, k]) of the k largest entries per row, ties by lower index"""
+    s = _chk(s, "s")
+    rows, cols = s.shape
+    idx = torch.empty((rows, k), dtype=torch.int32, device=s.device)
+    val = torch.empty((rows, k), dtype=torch.float32, device=s.device)
+    lib.rg_topk_rows(_p(s), rows, cols, k, _p(idx), _p(val), _stream())
+    return idx, val
+
+
+def row_sqsum(x):
+    x = _chk(x, "x")
+    out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    lib.rg_row_sqsum(_p(x), _p(out), x.shape[0], x.shape[1], _stream())
+    return out
+
+
+def add_outer_terms(m, rowv=None, colv=None, alpha=1.0, a=1.0, b=1.0):
+    m = _chk(m, "m")
+    lib.rg_add_outer_terms(_p(m), _p(rowv), _p(colv), alpha, a, b, m.shape[0], m.shape[1], _stream())
+    return m
+
+
+def segment_mean(x, order, offsets):
+    x = _chk(x, "x")
+    order, offsets = _chk(order, "order", torch.int64), _chk(offsets, "offsets", torch.int64)
+    out = torch.empty((offsets.numel() - 1, x.shape[1]), dtype=torch.float32, device=x.device)
+    lib.rg_segment_mean(_p(x), _p(order), _p(offsets), _p(out), offsets.numel() - 1, x.shape[1], _stream())
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# k-reciprocal re-ranking (csrc/rerank.hip): sparse encodings as row lists, see include/reidgan_hip.h
+# ------------------------------------------------------------------------------------------------
+def rerank_expand(rank, kf, kh, cap=None):
+    """(sets int32 [N, cap], counts int32 [N]): expanded k-reciprocal set of every row of the ranking `rank` int32 [N, R]
+    (kf / kh = columns read for the full / the half sets).  The default cap is the worst case kf * (kh + 1), capped at N."""
+    rank = _chk_rr(rank, "rank", torch.int32, 2)
+    N, R = rank.shape
+    kf, kh = int(kf), int(kh)
+    if not (1 <= kh <= kf <= R):
+        raise ValueError("rg_hip: rerank_expand needs 1 <= kh <= kf <= rank.shape[1], got kf=%d kh=%d R=%d" % (kf, kh, R))
+    cap = min(N, kf * (kh + 1)) if cap is None else int(cap)
+    sets = torch.empty((N, cap), dtype=torch.int32, device=rank.device)
+    counts = torch.empty((N,), dtype=torch.int32, device=rank.device)
+    lib.rg_rerank_expand(_p(rank), N, R, kf, kh, _p(sets), _p(counts), cap, _stream())
+    return sets, counts
+
+
+def rerank_weights(sets, counts, x=None, orig=None):
+    """w [N, cap]: softmax of -(2 - 2 x_i . x_e) over each row's set (x [N, D]), or exp(-orig[i, e]) / sum (orig [N, N])"""
+    sets, counts = _chk_rr(sets, "sets", torch.int32, 2), _chk_rr(counts, "counts", torch.int32, 1)
+    if (x is None) == (orig is None):
+        raise ValueError("rg_hip: rerank_weights takes exactly one of x and orig")
+    N, cap = sets.shape
+    w = torch.empty((N, cap), dtype=torch.float32, device=sets.device)      # entries beyond counts[i] are never read
+    if x is not None:
+        x = _chk_rr(x, "x", torch.float32, 2)
+        if x.data_ptr() & 15:            # the kernel reads the gathered rows as 16-byte vectors
+            x = x.clone()
+        if x.shape[0] != N or counts.numel() != N:
+            raise ValueError("rg_hip: rerank_weights: x %s, sets %s, counts %s disagree" % (tuple(x.shape), tuple(sets.shape), tuple(counts.shape)))
+        lib.rg_rerank_weights_feat(_p(x), N, x.shape[1], _p(sets), _p(counts), cap, _p(w), _stream())
+    else:
+        orig = _chk_rr(orig, "orig", torch.float32, 2)
+        if tuple(orig.shape) != (N, N) or counts.numel() != N:
+            raise ValueError("rg_hip: rerank_weights: orig %s must be [%d, %d]" % (tuple(orig.shape), N, N))
+        lib.rg_rerank_weights_dist(_p(orig), N, _p(sets), _p(counts), cap, _p(w), _stream())
+    return w
+
+
+def rerank_query_expand(sets, w, counts, rank=None, k2=1):
+    """CSR (rowptr int32 [N + 1], cols int32 [nnz], vals [nnz]) of the encodings after the local query expansion: row i = mean of
+    the rows rank[i, :k2]; rank None (k2 == 1) keeps every row.  Reads one integer back (nnz) to size the arrays."""
+    sets, counts, w = _chk_rr(sets, "sets", torch.int32, 2), _chk_rr(counts, "counts", torch.int32, 1), _chk_rr(w, "w", torch.float32, 2)
+    N, cap = sets.shape
+    if tuple(w.shape) != (N, cap) or counts.numel() != N:
+        raise ValueError("rg_hip: rerank_query_expand: sets %s, w %s, counts %s disagree" % (tuple(sets.shape), tuple(w.shape), tuple(counts.shape)))
+    k2, R = int(k2), 0
+    if rank is not None:
+        rank = _chk_rr(rank, "rank", torch.int32, 2)
+        R = rank.shape[1]
+        if rank.shape[0] != N or not (1 <= k2 <= min(R, 64)):
+            raise ValueError("rg_hip: rerank_query_expand needs rank [N, R] and 1 <= k2 <= min(R, 64), got %s, k2=%d" % (tuple(rank.shape), k2))
+    elif k2 != 1:
+        raise ValueError("rg_hip: rerank_query_expand without a ranking is the identity (k2 == 1), got k2=%d" % k2)
+    rowcnt = torch.empty((N,), dtype=torch.int32, device=sets.device)
+    rowptr = torch.empty((N + 1,), dtype=torch.int32, device=sets.device)
+    lib.rg_rerank_qe_count(_p(rank), R, k2, N, _p(sets), _p(counts), cap, _p(rowcnt), _p(rowptr), _stream())
+    nnz = int(rowptr[N].item())
+    if nnz <= 0 or nnz >= 2 ** 31:
+        raise RuntimeError("rg_hip: rerank_query_expand: %d non-zeros do not fit the int32 row pointers" % nnz)
+    cols = torch.empty((nnz,), dtype=torch.int32, device=sets.device)
+    vals = torch.empty((nnz,), dtype=torch.float32, device=sets.device)
+    lib.rg_rerank_qe_fill(_p(rank), R, k2, N, _p(sets), _p(w), _p(counts), cap, _p(rowptr), _p(cols), _p(vals), _stream())
+    return rowptr, cols, vals
+
+
+def rerank_columns(rowptr, cols, vals):
+    """column lists (colptr int32 [N + 1], crow int32 [nnz], cval [nnz]) of a CSR matrix; order inside a column unspecified"""
+    rowptr, cols, vals = _chk_rr(rowptr, "rowptr", torch.int32, 1), _chk_rr(cols, "cols", torch.int32, 1), _chk_rr(vals, "vals", torch.float32, 1)
+    N, nnz = rowptr.numel() - 1, cols.numel()
+    if N < 1 or vals.numel() != nnz:
+        raise ValueError("rg_hip: rerank_columns: rowptr %s, cols %s, vals %s disagree" % (tuple(rowptr.shape), tuple(cols.shape), tuple(vals.shape)))
+    colptr = torch.empty((N + 1,), dtype=torch.int32, device=cols.device)
+    cursor = torch.empty((N,), dtype=torch.int32, device=cols.device)
+    crow, cval = torch.empty_like(cols), torch.empty_like(vals)
+    lib.rg_rerank_columns(_p(rowptr), _p(cols), _p(vals), N, nnz, _p(colptr), _p(cursor), _p(crow), _p(cval), _stream())
+    return colptr, crow, cval
+
+
+def rerank_jaccard(csr, csc, rows=None, col_off=0, orig=None, lambda_value=0.0, clamp=True, chunk=0):
+    """[rows, N - col_off] Jaccard distances of the sparse encodings (csr / csc as returned above); with `orig` [N, N]:
+    (1 - lambda) * jaccard + lambda * orig.  chunk = columns accumulated per workgroup, 0 = automatic; same bits either way."""
+    rowptr, cols, vals = csr
+    colptr, crow, cval = csc
+    rowptr, colptr = _chk_rr(rowptr, "rowptr", torch.int32, 1), _chk_rr(colptr, "colptr", torch.int32, 1)
+    cols, crow = _chk_rr(cols, "cols", torch.int32, 1), _chk_rr(crow, "crow", torch.int32, 1)
+    vals, cval = _chk_rr(vals, "vals", torch.float32, 1), _chk_rr(cval, "cval", torch.float32, 1)
+    N = rowptr.numel() - 1
+    rows = N if rows is None else int(rows)
+    col_off, chunk = int(col_off), int(chunk)
+    if colptr.numel() != N + 1 or not (cols.numel() == vals.numel() == crow.numel() == cval.numel()):
+        raise ValueError("rg_hip: rerank_jaccard: row and column lists disagree")
+    if not (1 <= rows <= N and 0 <= col_off < N) or chunk < 0:
+        raise ValueError("rg_hip: rerank_jaccard: rows=%d col_off=%d chunk=%d outside N=%d" % (rows, col_off, chunk, N))
+    if orig is not None:
+        orig = _chk_rr(orig, "orig", torch.float32, 2)
+        if orig.shape[1] != N or orig.shape[0] < rows:
+            raise ValueError("rg_hip: rerank_jaccard: orig %s must be [>= %d, %d]" % (tuple(orig.shape), rows, N))
+    out = torch.empty((rows, N - col_off), dtype=torch.float32, device=cols.device)
+    lib.rg_rerank_jaccard(_p(rowptr), _p(cols), _p(vals), _p(colptr), _p(crow), _p(cval), N, rows, col_off, _p(orig),
+                          float(lambda_value), int(bool(clamp)), _p(out), chunk, _stream())
+    return out
+
+
+def rerank_orig_dist(q_g, q_q, g_g):
+    """transpose(A^2 / max(A^2, axis 0)) [Q + G, Q + G] of A = [[q_q, q_g], [q_g^T, g_g]] (re_ranking's normalised matrix)"""
+    q_g, q_q, g_g = _chk_rr(q_g, "q_g_dist", torch.float32, 2), _chk_rr(q_q, "q_q_dist", torch.float32, 2), _chk_rr(g_g, "g_g_dist", torch.float32, 2)
+    Q, G = q_g.shape
+    if tuple(q_q.shape) != (Q, Q) or tuple(g_g.shape) != (G, G):
+        raise ValueError("rg_hip: rerank_orig_dist: q_g %s needs q_q [%d, %d] and g_g [%d, %d], got %s and %s"
+                         % (tuple(q_g.shape), Q, Q, G, G, tuple(q_q.shape), tuple(g_g.shape)))
+    colmax = torch.empty((Q + G,), dtype=torch.float32, device=q_g.device)
+    orig = torch.empty((Q + G, Q + G), dtype=torch.float32, device=q_g.device)
+    lib.rg_rerank_orig_dist(_p(q_g), _p(q_q), _p(g_g), Q, G, _p(colmax), _p(orig), _stream())
+    return orig
+
+
+def rerank_from_rank(rank, kf, kh, k2, x=None, orig=None, rows=None, col_off=0, lambda_value=0.0, clamp=True, chunk=0, debug=False):
+    """Stages 2-6 of the re-ranking on an initial ranking `rank` int32 [N, R]: expanded k-reciprocal sets, their weights (from
+    the features x or the normalised distances orig), local query expansion over rank[:, :k2], column lists, Jaccard rows.
+    debug=True also returns {"rank", "sets", "counts", "w", "rowptr", "cols", "vals"} (device tensors)."""
+    sets, counts = rerank_expand(rank, kf, kh)
+    w = rerank_weights(sets, counts, x=x) if orig is None else rerank_weights(sets, counts, orig=orig)
+    csr = rerank_query_expand(sets, w, counts, rank=rank if k2 != 1 else None, k2=k2)
+    csc = rerank_columns(*csr)
+    out = rerank_jaccard(csr, csc, rows=rows, col_off=col_off, orig=orig, lambda_value=lambda_value, clamp=clamp, chunk=chunk)
+    if debug:
+        return out, dict(rank=rank, sets=sets, counts=counts, w=w, rowptr=csr[0], cols=csr[1], vals=csr[2])
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# CMC / mAP scoring of a query x gallery distance matrix (csrc/rank_eval.hip)
+# ------------------------------------------------------------------------------------------------
+def rank_eval(dist, query_ids, gallery_ids, query_cams, gallery_cams, topk=100, separate_camera_set=False, chunk=0, debug=False):
+    """Scores the ranking every row of dist [Q, G] (fp32 or fp64, on the device) defines, without sorting it:
+    {"status", "num_valid", "ap_sum", "first_hist" int64 [topk], "allshots" fp64 [topk]} — the number of queries with a
+    positive, the sum of their average precisions, the histogram of the first-match rank and sum_i hits[i, k] / npos[i]
+    (cumsum / num_valid of the last two are the reference's `market1501` and `allshots` CMC curves, ap_sum / num_valid its
+    mAP).  ids / cams are int32 device vectors.  Two small tensors (topk + 2 and topk + 1 numbers) are read back.  A NaN in
+    the matrix raises ValueError.  chunk = positives per pass held in LDS (0 = automatic), same bits for any value.
+    debug=True adds the per-query device tensors "npos", "ap", "first", "hits"."""
+    if not torch.is_tensor(dist) or dist.dtype not in (torch.float32, torch.float64):
+        raise TypeError("rg_hip: rank_eval: dist must be an fp32 or fp64 tensor, got %s"
+                        % (dist.dtype if torch.is_tensor(dist) else type(dist).__name__))
+    dist = _chk_rr(dist, "dist", dist.dtype, 2)
+    Q, G = dist.shape
+    topk, chunk = int(topk), int(chunk)
+    if Q < 1 or G < 1:
+        raise ValueError("rg_hip: rank_eval: dist must be a non-empty [Q, G] matrix, got shape %s" % (tuple(dist.shape),))
+    if topk < 1 or Q * topk >= 2 ** 31:
+        raise ValueError("rg_hip: rank_eval needs topk >= 1 and Q * topk < 2^31, got Q=%d topk=%d" % (Q, topk))
+    if not 0 <= chunk <= 1024:
+        raise ValueError("rg_hip: rank_eval: chunk must be 0 (automatic) or 1 .. 1024, got %d" % chunk)
+    vecs = []
+    for t, name, n in ((query_ids, "query_ids", Q), (gallery_ids, "gallery_ids", G), (query_cams, "query_cams", Q),
+                       (gallery_cams, "gallery_cams", G)):
+        t = _chk_rr(t, name, torch.int32, 1)
+        if t.numel() != n:
+            raise ValueError("rg_hip: rank_eval: %s has %d entries, dist %s needs %d" % (name, t.numel(), tuple(dist.shape), n))
+        vecs.append(t)
+    dev = dist.device
+    npos = torch.empty((Q,), dtype=torch.int32, device=dev)
+    ap = torch.empty((Q,), dtype=torch.float64, device=dev)
+    first = torch.empty((Q,), dtype=torch.int32, device=dev)
+    hits = torch.empty((Q, topk), dtype=torch.int32, device=dev)
+    counts = torch.empty((topk + 2,), dtype=torch.int32, device=dev)
+    sums = torch.empty((topk + 1,), dtype=torch.float64, device=dev)
+    lib.rg_rank_eval(_p(dist), int(dist.dtype == torch.float64), Q, G, G, _p(vecs[0]), _p(vecs[1]), _p(vecs[2]), _p(vecs[3]),
+                     int(bool(separate_camera_set)), topk, chunk, _p(npos), _p(ap), _p(first), _p(hits), _p(counts), _p(sums), _stream())
+    counts_h, sums_h = counts.cpu().numpy(), sums.cpu().numpy()
+    if counts_h[0] != 0:
+        raise ValueError("rg_hip: rank_eval: the distance matrix holds a NaN")
+    res = dict(status=int(counts_h[0]), num_valid=int(counts_h[1]), ap_sum=float(sums_h[0]),
+               first_hist=counts_h[2:].astype("int64"), allshots=sums_h[1:].copy())
+    if debug:
+        res.update(npos=npos, ap=ap, first=first, hits=hits)
+    return res
