@@ -459,6 +459,37 @@ int rg_infomap_segment_sum(const double* q, int E, const int* eidx, const int* s
 int rg_infomap_labels(const int* mod, int N, int cluster_num, int* size, int* minm, int* head, int* num, int64_t* labels,
                       rg_stream_t stream);
 
+/* ---- k-means (Lloyd) on features x fp32 [N][D] with centroids c fp32 [K][D]: `label_generator_kmeans` of
+ * CC/clustercontrast/models/kmeans.py (faiss.Kmeans, niter 300) as faiss's Clustering::train with spherical = false and
+ * nredo = 1 under a deterministic split rule (faiss's objective and iteration, not its seeded labels).  One iteration
+ * is assign, tally, update, split.  All index arrays int32; 1 <= K <= 8192, K <= N <= 1 048 576, 1 <= D <= 8192, anything else is
+ * RG_ERR_INVALID.  No floating-point atomics; the integer atomics used give results independent of their order.
+ *   rg_kmeans_assign   label[i] = argmin_j (csq[j] - 2 x_i . c_j), ties to the lowest j; score[i] = that minimum in fp32.  The
+ *                      products are exact fp32 (v_mfma_f32_32x32x2_f32: one fma chain over d per score), the argmin is taken in
+ *                      the kernel's epilogue and the [N][K] scores are never stored.  With more than one tile of 128 centroids
+ *                      the tiles meet in N 64-bit keys (score bits, index) by integer atomicMin: rg_kmeans_assign_workspace
+ *                      bytes (0 for K <= 128)
+ *   rg_kmeans_tally    cnt[j] = members of cluster j, rowptr [K + 1] = their exclusive prefix sum, order [N] = the members of
+ *                      cluster 0, then 1, ..., each in ascending row index, *changed = rows with label != prev, *obj =
+ *                      sum_i (double(xsq[i]) + double(score[i])) in fp64 and a fixed order.  rg_kmeans_tally_workspace bytes.
+ *                      A label outside [0, K) is left out of cnt / order
+ *   rg_kmeans_update   c[j] = mean of the rows x[order[m]], m in [rowptr[j], rowptr[j + 1]): accumulated in FP64 in list order,
+ *                      divided in fp64, rounded to fp32 once; csq[j] = float(sum_d double(c[j][d])^2).  A cluster without a
+ *                      member keeps its row and its csq
+ *   rg_kmeans_split    every cluster with cnt == 0, in ascending index, takes as donor the cluster with the currently largest cnt
+ *                      (ties: lowest index): c[empty][d] = c[donor][d] * (1 + s_d), c[donor][d] *= (1 - s_d), s_d = +1/1024 for
+ *                      even d and -1/1024 for odd d (fp32 products); cnt[empty] = cnt[donor] / 2, cnt[donor] -= cnt[empty]; csq of
+ *                      both rows is refreshed; *nsplit += the number of splits.  One workgroup */
+int64_t rg_kmeans_assign_workspace(int N, int K, int D);
+int rg_kmeans_assign(const float* x, const float* c, const float* csq, int N, int K, int D, int* label, float* score,
+                     void* workspace, size_t workspace_bytes, rg_stream_t stream);
+int64_t rg_kmeans_tally_workspace(int N, int K);
+int rg_kmeans_tally(const int* label, const int* prev, const float* xsq, const float* score, int N, int K, int* cnt, int* rowptr,
+                    int* order, int* changed, double* obj, void* workspace, size_t workspace_bytes, rg_stream_t stream);
+int rg_kmeans_update(const float* x, const int* order, const int* rowptr, int N, int K, int D, float* c, float* csq,
+                     rg_stream_t stream);
+int rg_kmeans_split(float* c, float* csq, int* cnt, int K, int D, int* nsplit, rg_stream_t stream);
+
 /* ---- CMC / mAP scoring of a query x gallery distance matrix dist [Q][ld] (fp32, or fp64 with is_double = 1; compared in its
  * own type), CC/clustercontrast/evaluation_metrics/ranking.py `cmc` / `mean_ap`, without a sort.  All id / camera arrays int32.
  * Per query i: valid_j = (gid_j != qid_i) | (gcam_j != qcam_i) (and gcam_j != qcam_i with separate_camera_set), pos_j = valid_j

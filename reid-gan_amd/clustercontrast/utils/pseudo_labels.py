@@ -11,6 +11,9 @@ neither copied to the host nor duplicated; only the N labels come back, because 
 
 `infomap_pseudo_labels` is the same for examples/cluster_contrast_gan_train_usl_infomap.py:318-348 (normalise, get_dist_nbr,
 cluster_by_infomap, generate_cluster_features): kNN table, Infomap and centroids stay on the device.
+
+`kmeans_pseudo_labels` is the fixed-K recipe: `label_generator_kmeans` (clustercontrast/models/kmeans.py, k-means with
+num_classes centroids on `ops.kmeans`) followed by generate_cluster_features; it has no outliers, so every row carries a label.
 """
 from __future__ import absolute_import, print_function
 
@@ -72,4 +75,27 @@ def infomap_pseudo_labels(features, k=15, min_sim=0.5, cluster_num=4, print_flag
     if print_flag:
         print("Infomap pseudo labels: {} clusters, {} outliers, codelength {:.4f} bits, time cost: {}".format(
             info["n_clusters"], int((pseudo_labels == -1).sum()), info["codelength"], time.time() - end))
+    return pseudo_labels, cluster_features, info
+
+
+@torch.no_grad()
+def kmeans_pseudo_labels(features, num_classes=500, niter=300, print_flag=False):
+    """(pseudo_labels numpy int64 [N], cluster_features device tensor [C, D], info) of `features` [N, D] (host or device
+    tensor), used as given — the caller normalises, as the scripts do before clustering.  The labels are those of
+    `ops.kmeans` with num_classes centroids (info is its info); cluster_features is the un-normalised mean of the rows of every
+    label that occurs, in ascending label order: C == num_classes unless the final assignment leaves a centroid without a
+    row.  Only the N labels are copied out."""
+    end = time.time()
+    x = features if torch.is_tensor(features) else torch.as_tensor(features)
+    if x.dim() != 2:
+        raise ValueError("kmeans_pseudo_labels: features must be [N, D], got shape %s" % (tuple(x.shape),))
+    if not torch.cuda.is_available():
+        raise RuntimeError("kmeans_pseudo_labels: features must live on the GPU; the HIP path has no CPU fallback")
+    x = x.float().to(torch.device("cuda", torch.cuda.current_device())).contiguous()
+    labels, _, info = ops.kmeans(x, int(num_classes), niter=int(niter))
+    cluster_features = generate_cluster_features_device(labels, x)
+    pseudo_labels = labels.cpu().numpy()
+    if print_flag:
+        print("k-means pseudo labels: {} clusters, {} iterations, objective {:.4f}, time cost: {}".format(
+            cluster_features.shape[0], info["iterations"], info["obj"][-1] if info["obj"] else float("nan"), time.time() - end))
     return pseudo_labels, cluster_features, info

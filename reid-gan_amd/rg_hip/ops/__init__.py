@@ -17,6 +17,7 @@ unit(s) it calls.
     retrieval  csrc/cm.hip, retrieval.hip, rerank.hip, rank_eval.hip: cluster memory, kNN helpers, re-ranking, CMC / mAP
     dbscan     csrc/dbscan.hip
     infomap    csrc/infomap.hip: the wrappers and the host-driven search
+    kmeans     csrc/kmeans.hip: assign / tally / update / split and the host loop over them
     optimizer  csrc/optim.hip
     profile    the launch profiler
     datagen    csrc/datagen.hip: on-device input synthesis
@@ -29,7 +30,7 @@ Callers outside this package go through `ops.<name>`, never through a submodule:
 linear_fwd, linear_dgrad and cm_update on THIS module (to count calls, or with CPU stand-ins), and that reaches every caller only
 because all of them look the name up here and no wrapper inside the package calls these five.
 
-`ops.dbscan` and `ops.infomap` are the functions; they replace the attributes the import system set for the submodules of the
+`ops.dbscan`, `ops.infomap` and `ops.kmeans` are the functions; they replace the attributes the import system set for the submodules of the
 same name (importlib.import_module("rg_hip.ops.dbscan") still returns the submodule).
 
 Importing this package neither loads libreidgan_hip.so nor needs a GPU.
@@ -60,6 +61,8 @@ from .dbscan import dbscan_count, dbscan_fill, dbscan_neighbors, dbscan_componen
 from .infomap import (INFOMAP_MAX_N, INFOMAP_MAX_K, INFOMAP_FLOW_MAX_ITERS, INFOMAP_FLOW_BATCH, INFOMAP_SWEEP_CAP,
                       INFOMAP_LEVEL_CAP, INFOMAP_ROUND_CAP, infomap_links, infomap_flow, infomap_codelength, infomap_search,
                       infomap_labels, infomap)
+from .kmeans import (KMEANS_MAX_N, KMEANS_MAX_K, KMEANS_MAX_D, kmeans_rand_perm, kmeans_assign, kmeans_tally, kmeans_update,
+                     kmeans_split, kmeans)
 from .optimizer import adam_advance, adam_step_dev, adam_step, sgd_step
 from .profile import profile_enable, check_not_profiling, profile_reset, profile_collect
 from .datagen import pose_maps, flip_pad_crop, erase_rects_
@@ -79,3 +82,4 @@ from .eltwise import _CONST_FILL, _CLOCK
 from .loss import _loss_ws
 from .dbscan import _chk_dbscan_matrix, _chk_dbscan_lists, _nbr_ptr
 from .infomap import _chk_infomap_table, _chk_infomap_graph, _infomap_level, _infomap_aggregate
+from .kmeans import _chk_kmeans_shape, _row_sqsum

@@ -26,7 +26,14 @@ scripts' --k1 15 --eps 0.5 --k2 4) times the Infomap pseudo-labelling on the kNN
 features: device events around `links`, `flow`, `search` and `labels` (each with the read-backs its host loop makes), one
 warm-up pass, median of `--reps` (default 30); the counts of sweeps, levels and flow iterations; and the wall time of
 `infomap_pseudo_labels` end to end (normalise + kNN + Infomap + centroids + the N labels to the host).  There is no host
-path to put beside it: the `infomap` package is not part of this environment."""
+path to put beside it: the `infomap` package is not part of this environment.
+
+`--kmeans [N,D,K] [--noise X]` (default 12936,2048,500, 30 reps) times one k-means iteration on the same clustered features,
+from the state three iterations into a run: device events around `assign`, `tally`, `update` and `split` of csrc/kmeans.hip;
+in the same pass and process, the composition the library offered before them — `ops.linear_fwd` (the [N, K] product),
+`ops.add_outer_terms`, `ops.topk_rows(k=1)`, then a stable `torch.sort` of the labels with the segment offsets and
+`ops.segment_mean` — which writes and re-reads the [N, K] score matrix; one warm-up pass, medians with min / max of the two
+per-pass sums; and the wall time of the whole `ops.kmeans` run with its iterations."""
 import os, sys, time, json
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "reid-gan_amd"))
@@ -204,6 +211,69 @@ def infomap_mode(spec, reps, noise):
     print(json.dumps(res))
 
 
+def kmeans_mode(spec, reps, noise):
+    import numpy as np
+    N, D, K = (int(v) for v in spec.split(","))
+    x = _clustered_features(N, D, noise)
+    # a mid-run state to time one iteration on: the centroids and labels after three iterations
+    _, c, _ = ops.kmeans(x, K, niter=3)
+    csq, xsq = ops.row_sqsum(c), ops.row_sqsum(x)
+    prev = ops.kmeans_assign(x, c, csq)[0]
+    nsplit = torch.zeros((1,), dtype=torch.int32, device=dev)
+    names = ["assign", "tally", "update", "split"]
+    composed = ["gemm", "outer_terms", "top1", "sort", "segment_mean"]
+    samples = {n: [] for n in names + composed}
+    tally = None
+    for it in range(reps + 1):
+        c1, q1 = c.clone(), csq.clone()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(names) + 1)]
+        ev[0].record()
+        label, score = ops.kmeans_assign(x, c1, q1); ev[1].record()
+        tally = ops.kmeans_tally(label, prev, xsq, score, K, out=tally); ev[2].record()
+        ops.kmeans_update(x, tally["order"], tally["rowptr"], c1, q1); ev[3].record()
+        ops.kmeans_split(c1, q1, tally["cnt"], nsplit); ev[4].record()
+        # the composition the library offered before: GEMM, score matrix, row top-1, then a stable sort and segment_mean
+        cv = [torch.cuda.Event(enable_timing=True) for _ in range(len(composed) + 1)]
+        cv[0].record()
+        s = ops.linear_fwd(x, c); cv[1].record()
+        ops.add_outer_terms(s, None, csq, alpha=2.0, b=-1.0); cv[2].record()          # 2 x.c - |c|^2: its maximum is the nearest centroid
+        lab2 = ops.topk_rows(s, 1)[0].flatten(); cv[3].record()
+        sl, order = torch.sort(lab2.long(), stable=True)
+        _, sizes = torch.unique_consecutive(sl, return_counts=True)
+        offsets = torch.zeros(sizes.numel() + 1, dtype=torch.int64, device=dev)
+        offsets[1:] = torch.cumsum(sizes, dim=0); cv[4].record()
+        means = ops.segment_mean(x, order, offsets); cv[5].record()
+        torch.cuda.synchronize()
+        if it:                                   # pass 0 is the warm-up
+            for i, n in enumerate(names):
+                samples[n].append(ev[i].elapsed_time(ev[i + 1]))
+            for i, n in enumerate(composed):
+                samples[n].append(cv[i].elapsed_time(cv[i + 1]))
+        agree = float((lab2 == label).float().mean())
+        del s, lab2, sl, order, offsets, means
+    med = {n: round(float(np.median(v)), 3) for n, v in samples.items()}
+    fused = np.sum([samples[n] for n in names], axis=0)
+    comp = np.sum([samples[n] for n in composed], axis=0)
+    wall, info = [], {}
+    for it in range(min(reps, 5) + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        _, _, info = ops.kmeans(x, K)
+        torch.cuda.synchronize()
+        if it:
+            wall.append((time.perf_counter() - t0) * 1e3)
+    res = {"kmeans": {"N": N, "D": D, "K": K, "noise": noise, "reps": reps},
+           "stage_ms_median": {n: med[n] for n in names}, "stage_ms_min_max": {n: [round(min(samples[n]), 3), round(max(samples[n]), 3)] for n in names},
+           "fused_iteration_ms": {"median": round(float(np.median(fused)), 3), "min": round(float(fused.min()), 3), "max": round(float(fused.max()), 3)},
+           "assign_TFLOPS": round(2.0 * N * K * D / med["assign"] / 1e9, 1),
+           "composed_stage_ms_median": {n: med[n] for n in composed},
+           "composed_iteration_ms": {"median": round(float(np.median(comp)), 3), "min": round(float(comp.min()), 3), "max": round(float(comp.max()), 3)},
+           "score_matrix_MB": round(N * K * 4 / 1e6, 1), "labels_agree": round(agree, 6),
+           "kmeans_wall_ms": round(float(np.median(wall)), 3), "iterations": info["iterations"], "converged": info["converged"],
+           "n_split": info["n_split"], "objective_first_last": [info["obj"][0], info["obj"][-1]]}
+    print(json.dumps(res))
+
+
 def evaluate_mode(spec, reps, noise):
     import numpy as np
     from rg_hip.lib import lib
@@ -282,6 +352,14 @@ if "--evaluate" in sys.argv:
     _reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 5
     _noise = float(sys.argv[sys.argv.index("--noise") + 1]) if "--noise" in sys.argv else 0.90
     evaluate_mode(_spec, _reps, _noise)
+    sys.exit(0)
+
+if "--kmeans" in sys.argv:
+    _i = sys.argv.index("--kmeans") + 1
+    _spec = sys.argv[_i] if _i < len(sys.argv) and not sys.argv[_i].startswith("--") else "12936,2048,500"
+    _reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 30
+    _noise = float(sys.argv[sys.argv.index("--noise") + 1]) if "--noise" in sys.argv else 0.30
+    kmeans_mode(_spec, _reps, _noise)
     sys.exit(0)
 
 if "--infomap" in sys.argv:

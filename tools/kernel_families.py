@@ -87,6 +87,9 @@ FAMILY = {
     "infomap_module_totals_kernel": "misc", "infomap_codelength_kernel": "misc", "infomap_propose_kernel": "misc",
     "infomap_apply_kernel": "misc", "infomap_segment_sum_kernel": "misc", "infomap_label_init_kernel": "misc",
     "infomap_label_count_kernel": "misc", "infomap_label_head_kernel": "misc", "infomap_label_write_kernel": "misc",
+    # kmeans.hip
+    "kmeans_assign_kernel": "misc", "kmeans_decode_kernel": "misc", "kmeans_rank_kernel": "misc", "kmeans_colscan_kernel": "misc",
+    "kmeans_order_kernel": "misc", "kmeans_update_kernel": "misc", "kmeans_csq_kernel": "misc", "kmeans_split_kernel": "misc",
     # rank_eval.hip
     "rank_eval_row_kernel": "misc", "rank_eval_reduce_kernel": "misc",
 }
