@@ -673,6 +673,16 @@ int rg_softmax_ce_fwd(const float* logits, const int64_t* labels, float* loss_ro
                       float scale, rg_stream_t stream);
 int rg_softmax_ce_bwd(const float* logits, const int64_t* labels, const float* lse, const float* grad_rows,
                       float* dlogits, int B, int K, float scale, float grad_scale, rg_stream_t stream);
+/* The same cross entropy over two logit blocks la[n][m] | lb[n][t] read where the GEMMs left them, with a group-diagonal mask:
+ * row i is the cross entropy of scale * la[i][j] followed by scale * (lb[i][j] + (j == i / group ? mask : 0)), the addition in
+ * fp32 before the multiply (`outputs_ex += -10000 * eye(t).repeat_interleave(group, 0)`, then `/= temp`,
+ * CC/clustercontrast/models/cm.py:165-177).  n == t * group.  A label lies in [0, m + t); outside it the row's loss and both
+ * gradient rows are 0.  dla / dlb = grad_rows[i] (1 when NULL) * grad_scale * scale * (softmax - onehot). */
+int rg_softmax_ce_ext_fwd(const float* la, const float* lb, const int64_t* labels, float* loss_rows, float* lse, int n, int m,
+                          int t, int group, float mask, float scale, rg_stream_t stream);
+int rg_softmax_ce_ext_bwd(const float* la, const float* lb, const int64_t* labels, const float* lse, const float* grad_rows,
+                          float grad_scale, float* dla, float* dlb, int n, int m, int t, int group, float mask, float scale,
+                          rg_stream_t stream);
 /* out[0] = scale * sum_i x[i]*w[i] (w may be NULL): .mean() / conf_mask weighting of per-sample losses */
 int rg_weighted_sum_fwd(const float* x, const float* w, float* out, int64_t n, float scale, rg_stream_t stream);
 int rg_weighted_sum_bwd(const float* grad_out, const float* w, float* dx, int64_t n, float scale, rg_stream_t stream);

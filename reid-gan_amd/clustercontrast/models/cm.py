@@ -174,12 +174,15 @@ class ClusterMemory_Gradient(nn.Module, ABC):
         inputs = RF.normalize_rows(inputs)
         outputs = _MatmulT.apply(inputs, self.normed_clusters.detach())
         if ex_f is not None:
-            ex_f = RF.normalize_rows(ex_f)
-            outputs_ex = _MatmulT.apply(inputs, ex_f)
-            group_size = outputs_ex.shape[0] // outputs_ex.shape[1]
-            mask = (-10000.0 * torch.eye(ex_f.shape[0], device=inputs.device)).repeat_interleave(group_size, dim=0)
-            outputs_ex = _AddConst.apply(outputs_ex, mask)
-            outputs = _Cat2.apply(outputs, outputs_ex)
+            # extra negatives (:165-177): row i also sees <inputs_i, ex_f_j> for every j, its own identity's column i // group_size
+            # pushed down by 10000 before the division by temp.  The two logit blocks go to one kernel where the GEMMs left them: no
+            # eye / repeat_interleave mask, no concatenation, no slices in backward
+            n, t = inputs.shape[0], ex_f.shape[0]
+            if t == 0 or n % t:
+                raise ValueError("ClusterMemory_Gradient: %d rows are not whole groups for %d extra features (the reference's "
+                                 "`outputs_ex += mask` fails with a shape error here)" % (n, t))
+            outputs_ex = _MatmulT.apply(inputs, RF.normalize_rows(ex_f))
+            return RF.cross_entropy_ext(outputs, outputs_ex, targets, n // t, -10000.0, 1.0 / self.temp)
         return RF.cross_entropy(outputs, targets, 1.0 / self.temp)
 
     def update_clusters(self, p_ids, eps=1e-16):
@@ -209,24 +212,3 @@ class _MatmulT(autograd.Function):
         da = ops.linear_dgrad(g, b) if ctx.needs_input_grad[0] else None
         db = ops.linear_wgrad(a, g) if ctx.needs_input_grad[1] else None
         return da, db
-
-
-class _AddConst(autograd.Function):
-    @staticmethod
-    def forward(ctx, x, c):
-        return ops.add(x, c)
-
-    @staticmethod
-    def backward(ctx, g):
-        return g, None
-
-
-class _Cat2(autograd.Function):
-    @staticmethod
-    def forward(ctx, a, b):
-        ctx.ca = a.shape[1]
-        return ops.cat_channels([a, b])
-
-    @staticmethod
-    def backward(ctx, g):
-        return ops.slice_channels(g, 0, ctx.ca), ops.slice_channels(g, ctx.ca, g.shape[1])

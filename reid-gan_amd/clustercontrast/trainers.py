@@ -1,6 +1,8 @@
 """Step drivers — restates CC/clustercontrast/trainers.py (ClusterContrastTrainer :213-270,
-ClusterContrastWithGANTrainer :15-210, GANTrainer :273-335) and the joint ReID + GAN step that only exists in
-CC/clustercontrast/trainers_b.py:617-814 (`train_all`), on the HIP runtime.
+ClusterContrastWithGANTrainer :15-210, GANTrainer :273-335), the joint ReID + GAN step that only exists in
+CC/clustercontrast/trainers_b.py:617-814 (`train_all`) and the ReID warm-up loop of :1087-1138 (`train_reid`), on the HIP runtime.
+`ClusterContrastWithGANTrainer.train` is the hard-mix loop of trainers.py:34-127 (`hard_mix_step`) when the memory is a
+ClusterMemory_Gradient, the only memory its `ex_f=` call is valid for.
 
 Same constructors, method names and arguments.  Differences that are scheduling only:
   * host->device copies are non-blocking; `loss.item()` (a device sync per step in the reference, :247)
@@ -12,6 +14,7 @@ The encoder's train-mode tuple output is accepted everywhere.
 """
 from __future__ import print_function, absolute_import
 
+import inspect
 import time
 
 import torch
@@ -19,8 +22,10 @@ from rg_hip.tape import backward as _backward
 import torch.nn as nn
 
 from rg_hip import functional as RF
+from rg_hip.nn import invalidate_folds
 from rg_hip.parallel import GradReducer, attach_stage_hooks
 
+from .utils.data.diff_augs import my_transform
 from .utils.meters import AverageMeter
 
 try:                                    # optional observability, never on the hot path
@@ -274,11 +279,117 @@ class ClusterContrastWithGANTrainer(object):
         optimizer.step()
         return loss.detach()
 
+    def hard_mix_step(self, reid_inputs, labels, optimizer, group_size=None):
+        """The hard-mix step, live lines of trainers.py:65-72, 96-98: encode the batch -> the GAN decodes one hard-mixed image per
+        identity from the detached features (`synthesize_fc`) -> `my_transform` -> the encoder embeds those images in eval mode
+        -> `memory(f_out, labels, ex_f=f_ex)`, the synthesised images as extra negatives with each row's own identity masked
+        -> backward through the encoder's first pass only -> optimizer step.  Returns the detached device loss.
+
+        `group_size` (default `opt.num_instances`): instances per identity; the batch must hold whole groups, checked before
+        anything runs.  Under torch.distributed each rank mixes within its local batch.
+
+        Scheduling only: the GAN branch and the second encoder pass take no part in the backward (the reference detaches both
+        ends), so they run without a tape and keep no activations.  The GAN's modules stay in the mode the caller left them; the
+        encoder's running statistics do not move in the eval pass, and its BatchNorm folds are redone for it on every call."""
+        if group_size is None:
+            group_size = self.opt.num_instances
+        n = reid_inputs.shape[0]
+        if group_size <= 0 or n % group_size:
+            raise ValueError("hard_mix_step: a batch of %d is not whole identity groups of %d" % (n, group_size))
+        reducer = self._reducers.get(optimizer, self.encoder)     # rank-0 broadcast before the first forward
+        f_out = _first(self._forward(reid_inputs))
+        f_ex = self._embed_hard_mix(f_out.detach(), group_size)
+        loss = self.memory(f_out, labels, ex_f=f_ex)
+        optimizer.zero_grad()
+        _backward(loss)
+        reducer.reduce()
+        optimizer.step()
+        return loss.detach()
+
+    def _embed_hard_mix(self, f_out, group_size):
+        """eval-mode embeddings of the GAN's hard-mixed images [identities, D], detached (trainers.py:66-70)"""
+        encoder = self.encoder
+        with torch.no_grad():
+            fc_image = self.gan.synthesize_fc(f_out, group_size)
+            x = my_transform(fc_image)
+            # the train-mode pass above moved the running statistics behind the fold's key (rg_hip.nn.invalidate_folds)
+            invalidate_folds(encoder)
+            encoder.eval()
+            try:
+                return _first(self._forward(x)).detach()
+            finally:
+                encoder.train()
+
+    def _takes_ex_f(self):
+        return "ex_f" in inspect.signature(self.memory.forward).parameters
+
     def train(self, epoch, data_loader, optimizer, print_freq=10, train_iters=400, acc_iters=0):
-        """ReID training with the GAN's inputs staged (the committed `train`, trainers.py:34-127, calls
-        `memory(f_out, labels, ex_f=...)`, valid only for ClusterMemory_Gradient, and `synthesize_fc` with
-        inconsistent arity — SURVEY §9.5); the well-defined part, the cluster-contrast update, is what runs."""
-        return self.train_all(epoch, data_loader, optimizer, print_freq, train_iters, acc_iters, joint=False)
+        """trainers.py:34-127.  With a memory whose forward takes `ex_f` (ClusterMemory_Gradient, the script's
+        `--learnable_memory` mode) this is the reference's loop on `hard_mix_step`.  With a ClusterMemory the reference's
+        `memory(f_out, labels, ex_f=...)` is a TypeError; there the well-defined part, the cluster-contrast update with the GAN's
+        inputs staged, is what runs (`train_all(joint=False)`)."""
+        if not self._takes_ex_f():
+            return self.train_all(epoch, data_loader, optimizer, print_freq, train_iters, acc_iters, joint=False)
+        if getattr(self.gan, "use_adp", False):
+            print("train adaptor and reid")
+        group_size = self.opt.num_instances
+
+        def step(inputs):
+            reid_inputs, labels, _ = self._parse_data(inputs[0])
+            self.gan.set_input(inputs[1])
+            return self.hard_mix_step(reid_inputs, labels, optimizer, group_size)
+        self._loop(epoch, data_loader, step, print_freq, train_iters, log="reid_loss", tail="\n")
+
+    def train_reid(self, epoch, data_loader, optimizer, print_freq=10, train_iters=400, acc_iters=0):
+        """The ReID warm-up loop, trainers_b.py:1087-1138: `loss = memory(f_out, labels)` on the ReID half `inputs[0]` of every
+        item, the GAN untouched.  A scalar loss (ClusterMemory_Gradient) is used as is; a per-row loss (ClusterMemory,
+        reduction='none') is averaged — the reference's `loss.backward()` on that vector is a RuntimeError (grad can be implicitly
+        created only for scalar outputs), so its loop only ever ran with the scalar."""
+        print("warm up stage for reid")
+
+        def step(inputs):
+            reid_inputs, labels, _ = self._parse_data(inputs[0])
+            reducer = self._reducers.get(optimizer, self.encoder)
+            loss = self.memory(_first(self._forward(reid_inputs)), labels)
+            if loss.dim():
+                loss = RF.weighted_mean(loss)
+            optimizer.zero_grad()
+            _backward(loss)
+            reducer.reduce()
+            optimizer.step()
+            return loss.detach()
+        self._loop(epoch, data_loader, step, print_freq, train_iters)
+
+    def _loop(self, epoch, data_loader, step, print_freq, train_iters, log=None, tail=""):
+        """the loop shell of `train` / `train_reid`: meters, the deferred `loss.item()` (one transfer per print interval unless
+        `sync_every_step`), the reference's print line"""
+        self.encoder.train()
+        batch_time = AverageMeter()
+        data_time = AverageMeter()
+        losses = AverageMeter()
+        pending = []
+        end = time.time()
+        for i in range(train_iters):
+            inputs = data_loader.next()
+            data_time.update(time.time() - end)
+            pending.append(step(inputs))
+            if self.sync_every_step or (i + 1) % print_freq == 0 or i + 1 == train_iters:
+                for v in torch.stack(pending).tolist():
+                    losses.update(v)
+                    if log is not None and _wandb is not None and getattr(_wandb, "run", None) is not None:
+                        _wandb.log({log: v})
+                pending = []
+            batch_time.update(time.time() - end)
+            end = time.time()
+            if (i + 1) % print_freq == 0:
+                print('Epoch: [{}][{}/{}]\t'
+                      'Time {:.3f} ({:.3f})\t'
+                      'Data {:.3f} ({:.3f})\t'
+                      'Loss {:.3f} ({:.3f})'
+                      .format(epoch, i + 1, len(data_loader),
+                              batch_time.val, batch_time.avg,
+                              data_time.val, data_time.avg,
+                              losses.val, losses.avg) + tail)
 
     def _parse_data(self, inputs):
         imgs, _, pids, _, indexes = inputs

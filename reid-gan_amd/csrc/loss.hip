@@ -239,6 +239,74 @@ __global__ __launch_bounds__(256) void softmax_ce_bwd_kernel(const float* __rest
     }
 }
 
+// ---- cross entropy over two logit blocks with a group-diagonal mask (CC/clustercontrast/models/cm.py:165-177) ----
+// Row b is the cross entropy of the K = m + t values scale * la[b][j], then scale * (lb[b][j] + (j == b / group ? mask : 0)):
+// the addition first, in fp32, as the reference's `outputs_ex += mask` before `/= temp`.  The two blocks are read where the
+// GEMMs left them; one workgroup per row, block A and block B in a loop of their own (no per-element branch on the block).
+struct CeExtRow {
+    const float* a;
+    const float* b;
+    int m, col;
+    float mask, scale;
+    __device__ __forceinline__ float va(int i) const { return a[i] * scale; }
+    __device__ __forceinline__ float vb(int j) const { return (b[j] + (j == col ? mask : 0.f)) * scale; }
+    __device__ __forceinline__ float at(int i) const { return i < m ? va(i) : vb(i - m); }
+};
+
+__global__ __launch_bounds__(256) void softmax_ce_ext_fwd_kernel(const float* __restrict__ la, const float* __restrict__ lb,
+                                                                 const int64_t* __restrict__ labels, float* __restrict__ loss,
+                                                                 float* __restrict__ lse, int m, int t, int group, float mask,
+                                                                 float scale) {
+    __shared__ float red[16];
+    const int b = blockIdx.x;
+    const CeExtRow r = {la + (int64_t)b * m, lb + (int64_t)b * t, m, b / group, mask, scale};
+    float mx = -INFINITY;
+    for (int i = threadIdx.x; i < m; i += 256) mx = fmaxf(mx, r.va(i));
+    for (int j = threadIdx.x; j < t; j += 256) mx = fmaxf(mx, r.vb(j));
+    mx = rg_block_max(mx, red);
+    float s = 0.f;
+    for (int i = threadIdx.x; i < m; i += 256) s += expf(r.va(i) - mx);
+    for (int j = threadIdx.x; j < t; j += 256) s += expf(r.vb(j) - mx);
+    s = rg_block_sum(s, red);
+    if (threadIdx.x == 0) {
+        const float l = mx + logf(s);
+        const int64_t y = labels[b];
+        lse[b] = l;
+        loss[b] = (y >= 0 && y < (int64_t)m + t) ? l - r.at((int)y) : 0.f;
+    }
+}
+
+// dla / dlb = g_b * scale * (softmax - onehot) over the two blocks; both rows zero for a label outside [0, m + t)
+__global__ __launch_bounds__(256) void softmax_ce_ext_bwd_kernel(const float* __restrict__ la, const float* __restrict__ lb,
+                                                                 const int64_t* __restrict__ labels, const float* __restrict__ lse,
+                                                                 const float* __restrict__ grow, float* __restrict__ dla,
+                                                                 float* __restrict__ dlb, int m, int t, int group, float mask,
+                                                                 float scale, float gscale) {
+    const int b = blockIdx.x;
+    const CeExtRow r = {la + (int64_t)b * m, lb + (int64_t)b * t, m, b / group, mask, scale};
+    float* da = dla + (int64_t)b * m;
+    float* db = dlb + (int64_t)b * t;
+    const int64_t y = labels[b];
+    if (y < 0 || y >= (int64_t)m + t) {
+        for (int i = threadIdx.x; i < m; i += 256) da[i] = 0.f;
+        for (int j = threadIdx.x; j < t; j += 256) db[j] = 0.f;
+        return;
+    }
+    const float g = (grow ? grow[b] : 1.f) * gscale * scale;
+    const float l = lse[b];
+    const int ya = (int)y, yb = (int)y - m;
+    for (int i = threadIdx.x; i < m; i += 256) {
+        float p = expf(r.va(i) - l);
+        if (i == ya) p -= 1.f;
+        da[i] = g * p;
+    }
+    for (int j = threadIdx.x; j < t; j += 256) {
+        float p = expf(r.vb(j) - l);
+        if (j == yb) p -= 1.f;
+        db[j] = g * p;
+    }
+}
+
 // out[0] = sum_i x[i]*w[i] * scale   (w may be NULL)
 __global__ __launch_bounds__(256) void wsum_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                    float* __restrict__ out, int64_t n, float scale) {
@@ -424,6 +492,27 @@ extern "C" int rg_softmax_ce_bwd(const float* logits, const int64_t* labels, con
     hipLaunchKernelGGL(softmax_ce_bwd_kernel, dim3(B), dim3(256), 0, stream, logits, labels, lse, grad_rows, dlogits, K,
                        scale, grad_scale);
     return rg::check_launch("rg_softmax_ce_bwd");
+}
+
+extern "C" int rg_softmax_ce_ext_fwd(const float* la, const float* lb, const int64_t* labels, float* loss_rows, float* lse, int n,
+                                     int m, int t, int group, float mask, float scale, hipStream_t stream) {
+    RG_REQUIRE(la && lb && labels && loss_rows && lse && n > 0 && m > 0 && t > 0 && group > 0, "rg_softmax_ce_ext_fwd: bad arguments");
+    RG_REQUIRE((int64_t)t * group == n, "rg_softmax_ce_ext_fwd: n must be t * group (every extra column masks one whole group of rows)");
+    rg::ProfScope prof(rg::FAM_LOSS, stream, 0.0, 4.0 * n * ((double)m + t));
+    hipLaunchKernelGGL(softmax_ce_ext_fwd_kernel, dim3(n), dim3(256), 0, stream, la, lb, labels, loss_rows, lse, m, t, group, mask,
+                       scale);
+    return rg::check_launch("rg_softmax_ce_ext_fwd");
+}
+
+extern "C" int rg_softmax_ce_ext_bwd(const float* la, const float* lb, const int64_t* labels, const float* lse,
+                                     const float* grad_rows, float grad_scale, float* dla, float* dlb, int n, int m, int t, int group,
+                                     float mask, float scale, hipStream_t stream) {
+    RG_REQUIRE(la && lb && labels && lse && dla && dlb && n > 0 && m > 0 && t > 0 && group > 0, "rg_softmax_ce_ext_bwd: bad arguments");
+    RG_REQUIRE((int64_t)t * group == n, "rg_softmax_ce_ext_bwd: n must be t * group (every extra column masks one whole group of rows)");
+    rg::ProfScope prof(rg::FAM_LOSS, stream, 0.0, 8.0 * n * ((double)m + t));
+    hipLaunchKernelGGL(softmax_ce_ext_bwd_kernel, dim3(n), dim3(256), 0, stream, la, lb, labels, lse, grad_rows, dla, dlb, m, t, group,
+                       mask, scale, grad_scale);
+    return rg::check_launch("rg_softmax_ce_ext_bwd");
 }
 
 extern "C" int rg_weighted_sum_fwd(const float* x, const float* w, float* out, int64_t n, float scale,

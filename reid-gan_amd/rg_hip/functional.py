@@ -161,6 +161,32 @@ def cross_entropy(logits, labels, scale=1.0):
     return weighted_mean(cross_entropy_rows(logits, labels, scale))
 
 
+class _SoftmaxCEExt(torch.autograd.Function):
+    """mean cross entropy over two logit blocks with a group-diagonal mask: the per-row kernel, then the mean of its rows (the
+    `_WeightedSum` kernels, so the upstream scalar gradient never leaves the device); gradients to both blocks"""
+
+    @staticmethod
+    def forward(ctx, la, lb, labels, group, mask, scale):
+        rows, lse = ops.softmax_ce_ext_fwd(la, lb, labels, group, mask, scale)
+        ctx.save_for_backward(la, lb, labels, lse)
+        ctx.group, ctx.mask, ctx.scale = group, mask, scale
+        return ops.weighted_sum_fwd(rows, None, 1.0 / rows.numel())
+
+    @staticmethod
+    def backward(ctx, g):
+        la, lb, labels, lse = ctx.saved_tensors
+        n = la.shape[0]
+        grow = ops.weighted_sum_bwd(_scalar_grad(g), None, n, 1.0 / n, g.device)
+        dla, dlb = ops.softmax_ce_ext_bwd(la, lb, labels, lse, grow, ctx.group, ctx.mask, ctx.scale)
+        return dla, dlb, None, None, None, None
+
+
+def cross_entropy_ext(la, lb, labels, group, mask, scale=1.0):
+    """F.cross_entropy(cat([la, lb + mask * eye(t).repeat_interleave(group, 0)], 1) * scale, labels) for la [n, m], lb [n, t],
+    n == t * group, without the mask, the concatenation or the slices of its backward."""
+    return _SoftmaxCEExt.apply(la, lb, labels, int(group), float(mask), float(scale))
+
+
 class _L2NormRows(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, eps):

@@ -606,6 +606,20 @@ class FoldGroup(object):
             conv._rg_fold = f
 
 
+def invalidate_folds(net):
+    """Forget every fold made for `net`.  A fold is keyed on the weights' arena epoch / version / address; the train-mode
+    BatchNorm kernels write the running statistics behind torch's version counters, so an eval-mode pass that follows a
+    train-mode pass of the SAME weight version (no optimizer step in between: the second encoder pass of the hard-mix step after
+    an evaluation, say) would be served the fold of the older statistics.  Callers that alternate the two modes call this
+    between them; the next eval-mode forward folds again (one launch per network)."""
+    for m in net.modules():
+        d = m.__dict__
+        if "_rg_fold_group" in d:
+            d["_rg_fold_group"].keys = None
+        if "_rg_fold" in d:
+            del d["_rg_fold"]
+
+
 def lib_fold_chunk():
     from .lib import lib
     return lib.rg_fold_chunk()

@@ -53,7 +53,7 @@ from .pool import (maxpool2d_fwd, maxpool2d_bwd, global_avgpool_fwd, global_avgp
                    part_pool_fwd, part_pool_bwd, mp_head_fwd, mp_head_bwd)
 from .loss import (sigmoid_bce_fwd, sigmoid_bce_bwd, mse_const_fwd, mse_const_bwd, affine_relu_mean_fwd, affine_relu_mean_bwd,
                    grad_penalty_rows, l1_fwd, l1_bwd, l1_rows_fwd, l1_rows_bwd, mse_const_rows_fwd, mse_const_rows_bwd,
-                   softmax_ce_fwd, softmax_ce_bwd, weighted_sum_fwd, weighted_sum_bwd)
+                   softmax_ce_fwd, softmax_ce_bwd, softmax_ce_ext_fwd, softmax_ce_ext_bwd, weighted_sum_fwd, weighted_sum_bwd)
 from .retrieval import (cm_update, normalize_listed_rows, topk_rows, row_sqsum, add_outer_terms, segment_mean, rerank_expand,
                         rerank_weights, rerank_query_expand, rerank_columns, rerank_jaccard, rerank_orig_dist, rerank_from_rank,
                         rank_eval)

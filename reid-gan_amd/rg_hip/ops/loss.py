@@ -143,6 +143,41 @@ def softmax_ce_bwd(logits, labels, lse, grad_rows, scale=1.0, grad_scale=1.0):
     return dz
 
 
+def _ce_ext_shape(la, lb, group):
+    """(n, m, t) of the two logit blocks la [n, m] | lb [n, t]; n == t * group, or the group-diagonal mask has no meaning (the
+    reference dies in a shape error there)"""
+    if la.dim() != 2 or lb.dim() != 2 or la.shape[0] != lb.shape[0]:
+        raise ValueError("softmax_ce_ext: logit blocks must be [n, m] and [n, t], got %s and %s" % (tuple(la.shape), tuple(lb.shape)))
+    n, m = la.shape
+    t = lb.shape[1]
+    if group <= 0 or t * group != n:
+        raise ValueError("softmax_ce_ext: %d rows are not %d groups of %d" % (n, t, group))
+    return n, m, t
+
+
+def softmax_ce_ext_fwd(la, lb, labels, group, mask, scale=1.0):
+    """per-row cross entropy of cat([la, lb + mask * (column == row // group)], 1) * scale without the concatenation or the mask
+    tensor -> (loss_rows [n], lse [n])"""
+    la, lb = _chk(la, "la"), _chk(lb, "lb")
+    labels = _chk(labels, "labels", torch.int64)
+    n, m, t = _ce_ext_shape(la, lb, group)
+    loss = torch.empty(n, dtype=torch.float32, device=la.device)
+    lse = torch.empty(n, dtype=torch.float32, device=la.device)
+    lib.rg_softmax_ce_ext_fwd(_p(la), _p(lb), _p(labels), _p(loss), _p(lse), n, m, t, group, mask, scale, _stream())
+    return loss, lse
+
+
+def softmax_ce_ext_bwd(la, lb, labels, lse, grad_rows, group, mask, scale=1.0, grad_scale=1.0):
+    """(dla [n, m], dlb [n, t]) = grad_rows (ones when None) * grad_scale * scale * (softmax - onehot)"""
+    la, lb = _chk(la, "la"), _chk(lb, "lb")
+    grad_rows = _chk(grad_rows, "grad_rows")
+    n, m, t = _ce_ext_shape(la, lb, group)
+    dla, dlb = torch.empty_like(la), torch.empty_like(lb)
+    lib.rg_softmax_ce_ext_bwd(_p(la), _p(lb), _p(labels), _p(lse), _p(grad_rows), grad_scale, _p(dla), _p(dlb), n, m, t, group,
+                              mask, scale, _stream())
+    return dla, dlb
+
+
 def weighted_sum_fwd(x, w=None, scale=1.0):
     x, w = _chk(x, "x"), _chk(w, "w")
     out = torch.empty((), dtype=torch.float32, device=x.device)

@@ -62,6 +62,7 @@ FAMILY = {
     "bce_partial_kernel": "loss", "finalize_sum_kernel": "loss", "grad_penalty_rows_kernel": "loss", "l1_bwd_kernel": "loss", "l1_rows_fwd_kernel": "loss", "mse_const_rows_fwd_kernel": "loss", "mse_const_rows_bwd_kernel": "loss", "l1_rows_bwd_kernel": "loss",
     "l1_finalize_kernel": "loss", "l1_partial_kernel": "loss", "mse_const_bwd_kernel": "loss",
     "mse_const_partial_kernel": "loss", "softmax_ce_bwd_kernel": "loss", "softmax_ce_fwd_kernel": "loss",
+    "softmax_ce_ext_bwd_kernel": "loss", "softmax_ce_ext_fwd_kernel": "loss",
     "wsum_bwd_kernel": "loss", "wsum_kernel": "loss",
     # cm.hip
     "cm_update_hard_kernel": "cm", "cm_update_kernel": "cm", "normalize_listed_rows_kernel": "cm",
