@@ -136,7 +136,7 @@ class ResNet_MP(RGModule):
             gan = self.feat_bn_gan                                         # running statistics only: its output is discarded
             ops.bn_stats(x_p, gan.running_mean, gan.running_var, gan.eps, gan.momentum)
             for bn in (gan,) + self._head_bns():
-                bn.__dict__["_nbt_pending"] = bn.__dict__.get("_nbt_pending", 0) + 1
+                bn.count_batch()
         bns = self._head_bns()
         fus = 1 if fusion == 'sum' else 0
         out, xhat, _mean, invstd, norms = ops.mp_head_fwd(

@@ -41,14 +41,14 @@ class _FFN(object):
         """gradient w.r.t. x INCLUDING the residual branch"""
         x, h = tape.pop()
         if tape.wants(lin2.weight):
-            tape.add_grad(lin2.weight, _conv1x1_wgrad(h, dy, out=tape.grad_out(lin2.weight)))
+            tape.add_grad(lin2.weight, _conv1x1_wgrad(h, dy, out=tape.grad_dst(lin2.weight)))
         if tape.wants(lin2.bias):
-            tape.add_grad(lin2.bias, ops.channel_sum(dy.unsqueeze(-1), out=tape.grad_out(lin2.bias)))
+            tape.add_grad(lin2.bias, ops.channel_sum(dy.unsqueeze(-1), out=tape.grad_dst(lin2.bias)))
         dh = ops.act_bwd(_conv1x1_dgrad(dy, lin2.weight.detach()), h, act, slope)
         if tape.wants(lin1.weight):
-            tape.add_grad(lin1.weight, _conv1x1_wgrad(x, dh, out=tape.grad_out(lin1.weight)))
+            tape.add_grad(lin1.weight, _conv1x1_wgrad(x, dh, out=tape.grad_dst(lin1.weight)))
         if tape.wants(lin1.bias):
-            tape.add_grad(lin1.bias, ops.channel_sum(dh.unsqueeze(-1), out=tape.grad_out(lin1.bias)))
+            tape.add_grad(lin1.bias, ops.channel_sum(dh.unsqueeze(-1), out=tape.grad_dst(lin1.bias)))
         w1 = lin1.weight.detach()
         dx = ops.conv2d_dgrad(dh.unsqueeze(-1), w1.view(w1.shape[0], w1.shape[1], 1, 1), (dh.shape[2], 1), 1, 0,
                               residual=dy.unsqueeze(-1))

@@ -128,9 +128,9 @@ class MultiheadAttention(RGModule):
         W = self.in_proj_weight.detach()
         Wo = self.out_proj.weight
         if tape.wants(Wo):
-            tape.add_grad(Wo, _conv1x1_wgrad(o, d_out, out=tape.grad_out(Wo)))
+            tape.add_grad(Wo, _conv1x1_wgrad(o, d_out, out=tape.grad_dst(Wo)))
         if tape.wants(self.out_proj.bias):
-            tape.add_grad(self.out_proj.bias, ops.channel_sum(d_out.unsqueeze(-1), out=tape.grad_out(self.out_proj.bias)))
+            tape.add_grad(self.out_proj.bias, ops.channel_sum(d_out.unsqueeze(-1), out=tape.grad_dst(self.out_proj.bias)))
         d_o = _conv1x1_dgrad(d_out, Wo.detach())
         dev = d_o.device
         # gradient buffers laid out like the forward projections so the in-projection backward is one conv per buffer
@@ -159,11 +159,11 @@ class MultiheadAttention(RGModule):
         wants_w, wants_b = tape.wants(self.in_proj_weight), tape.wants(self.in_proj_bias)
         gw = gb = None
         if wants_w:
-            gw = tape.grad_out(self.in_proj_weight)
+            gw = tape.grad_dst(self.in_proj_weight)
             if gw is None:
                 gw = torch.empty_like(W)
         if wants_b:
-            gb = tape.grad_out(self.in_proj_bias)
+            gb = tape.grad_dst(self.in_proj_bias)
             if gb is None:
                 gb = torch.empty(3 * E, dtype=torch.float32, device=dev)
         if mode == 0:

@@ -14,7 +14,7 @@ training flag, input shapes and requires_grad pattern, whether parameter gradien
 contribution of the step.  What a replay does NOT re-run is the Python of the programs, so its host-side effects are either forced to
 be unconditional during capture (filter re-layout / fp8 re-quantisation caches refresh every time: `ops.CAPTURING`), re-applied per
 replay (BatchNorm `num_batches_tracked` bookkeeping), or a reason not to graph the network (active Dropout draws a seed from the host
-generator per call; an active launch profiler needs the eager launches; a BatchNorm fold is refused by the fold itself, nn._fold_of).
+generator per call; an active launch profiler needs the eager launches; a BatchNorm fold is refused by the fold itself, nn.fold._fold_of).
 
 Memory: a record's inputs are copied into static buffers, its intermediates / outputs / saved activations live in the record's private
 graph pool (torch.cuda.graph), exactly as they would stay resident for the backward in eager mode; a network called k times before
@@ -27,6 +27,7 @@ import os
 import torch
 
 from . import ops
+from .nn import Dropout, _BatchNorm, nbt_add, nbt_pending
 from .tape import Tape, run_backward
 
 ENABLED = os.environ.get("RG_NET_GRAPHS", "1") != "0"
@@ -45,7 +46,6 @@ class _Record(object):
 
 
 def _bn_layers(net):
-    from .nn import _BatchNorm
     return [m for m in net.modules() if isinstance(m, _BatchNorm)]
 
 
@@ -59,7 +59,6 @@ _CAPTURE_MODE = "thread_local"
 
 def graphable(net):
     """no active Dropout (it draws a seed from the host generator per call; a replay would repeat the captured one)"""
-    from .nn import Dropout
     for m in net.modules():
         if isinstance(m, Dropout) and m.training and m.p > 0.0:
             return False
@@ -101,7 +100,7 @@ def _capture_forward(net, xs, params):
     rec.need = [isinstance(x, torch.Tensor) and x.requires_grad for x in xs]
     rec.tape = Tape(param_grad=len(params) > 0, needs_input=list(rec.need))
     bns = _bn_layers(net)
-    before = [b.__dict__.get("_nbt_pending", 0) for b in bns]
+    before = [nbt_pending(b) for b in bns]
     g = torch.cuda.CUDAGraph()
     try:
         with _capture_mode():
@@ -111,11 +110,10 @@ def _capture_forward(net, xs, params):
         # the aborted program's Python side effects must not survive it: none of its kernels ran.  Cache keys are not stamped while
         # capturing (wcache.Stamp); the BatchNorm step counters are put back here.
         for b, n0 in zip(bns, before):
-            b.__dict__["_nbt_pending"] = n0
+            nbt_add(b, n0 - nbt_pending(b))
         raise
     rec.pool = g.pool()
-    rec.bn_deltas = [(b, b.__dict__.get("_nbt_pending", 0) - n0) for b, n0 in zip(bns, before)
-                     if b.__dict__.get("_nbt_pending", 0) != n0]
+    rec.bn_deltas = [(b, nbt_pending(b) - n0) for b, n0 in zip(bns, before) if nbt_pending(b) != n0]
     rec.fwd = g
     rec.outs = outs
     rec.n_out = len(outs) if isinstance(outs, (tuple, list)) else 1
@@ -129,7 +127,7 @@ def _replay_forward(rec, xs):
             s.copy_(x)
     rec.fwd.replay()
     for b, d in rec.bn_deltas:
-        b.__dict__["_nbt_pending"] = b.__dict__.get("_nbt_pending", 0) + d
+        nbt_add(b, d)
 
 
 def _grad_pattern(params):

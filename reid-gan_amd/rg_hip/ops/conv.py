@@ -81,7 +81,7 @@ def conv2d_dgrad(dy, w, x_hw, stride=1, padding=0, scale=None, shift=None, resid
                         _p(shift), _p(residual), act, slope, _p(relu_mask), _p(rowsum), cols, _p(ws),
                         ws.numel() if ws is not None else 0, _stream())
     if rowsum is not None:
-        dx._rg_rowsum = rowsum          # rides with the gradient to the BatchNorm fold of the layer below (nn.conv_bn_tb)
+        dx._rg_rowsum = rowsum          # rides with the gradient to the BatchNorm fold of the layer below (nn.fold.conv_bn_tb)
     return dx
 
 

@@ -44,7 +44,7 @@ class Bottleneck(RGModule):
 
     def tb(self, tape, dy, need_dx=True, dy_masked=False, mask_input=False):
         """dy_masked: dy already went through this block's final ReLU backward; mask_input: the block's input is the
-        previous block's ReLU output, whose backward is applied in conv1's dgrad epilogue (see nn.conv_bn_tb)."""
+        previous block's ReLU output, whose backward is applied in conv1's dgrad epilogue (see nn.fold.conv_bn_tb)."""
         d, d_idn = rnn.conv_bn_tb(tape, self.conv3, self.bn3, dy, dy_masked=dy_masked, mask_input=True)
         if self.downsample is not None:
             d_idn = rnn.conv_bn_tb(tape, self.downsample[0], self.downsample[1], d_idn, need_dx=need_dx)

@@ -46,6 +46,20 @@ class Tape(object):
             return None
         return v
 
+    def grad_dst(self, p):
+        """grad_out(p) when the gradient of `p` is wanted, else None: what a kernel that writes parameter gradients is handed
+        as its output, whether or not the layer goes on to ask wants(p)"""
+        if self.param_grad and p is not None and p.requires_grad:
+            return self.grad_out(p)
+        return None
+
+    def add_grads(self, pairs):
+        """add_grad(p, g) for every (p, g) of `pairs` whose gradient is wanted, in the order given (add_grad may enqueue)"""
+        if self.param_grad:
+            for p, g in pairs:
+                if p is not None and p.requires_grad:
+                    self.add_grad(p, g)
+
     def add_grad(self, p, g):
         k = id(p)
         if g.shape != p.shape:
@@ -156,8 +170,8 @@ def run(net, *xs):
     if not need_graph:
         return net.tf(Tape(param_grad=False, record=False), *xs)
     if "_krsc_grouped" not in net.__dict__:
-        from . import nn as _rnn
-        _rnn.group_krsc(net)              # one re-layout launch per optimizer step for all filters of the network
+        from .nn import group_krsc        # here, not at the top: every module of rg_hip.nn imports RGModule from this one
+        group_krsc(net)                   # one re-layout launch per optimizer step for all filters of the network
     if net.__dict__.get("_rg_graph", False):
         # small-kernel networks: forward / backward programs replayed as two single-stream hipGraphs (rg_hip.netgraph)
         from . import netgraph

@@ -29,7 +29,7 @@ def test_weight_key_follows_version_arena_epoch_and_address():
 
 
 class _Cache(object):
-    """a single cache driven the way nn._KrscCache._krsc and lowp.F8Layer.weights drive theirs"""
+    """a single cache driven the way nn.conv._KrscCache._krsc and lowp.F8Layer.weights drive theirs"""
 
     def __init__(self, w):
         self.w, self.stamp, self.refreshes = w, wcache.Stamp(), 0
@@ -59,7 +59,7 @@ def test_stamp_is_stale_and_stays_unstamped_while_capturing():
 
 
 class _Group(object):
-    """a group driven the way nn.KrscGroup.get / refresh drive theirs: one refresh serves (and stamps) every member"""
+    """a group driven the way nn.conv.KrscGroup.get / refresh drive theirs: one refresh serves (and stamps) every member"""
 
     def __init__(self, ws):
         self.ws, self.stamps, self.stamp, self.refreshes = ws, [wcache.Stamp() for _ in ws], wcache.GroupStamp(), 0

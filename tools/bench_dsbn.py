@@ -4,10 +4,10 @@ takes through ResNet-50 with layer4 at stride 1, forward and backward, in ONE pr
     python tools/bench_dsbn.py --step [--dsbn] [--crops 256] [--steps 20]      ClusterContrastTrainer.step of resnet50 (converted)
 against
     (a) the composition the reference performs (CC/clustercontrast/models/dsbn.py:17-23): two slice copies of the halves, two
-        BatchNorms (rg_hip.nn.BatchNorm2d / 1d as the modules run them), one concatenation; backward: the two BatchNorm backwards on
+        BatchNorms (rg_hip.nn.norm.BatchNorm2d / 1d as the modules run them), one concatenation; backward: the two BatchNorm backwards on
         the halves of dy (views, as torch's cat backward hands them over) and one concatenation of the two dx (split's backward);
     (b) the existing rg_bn_* entry points called on the two halves by pointer offset (the halves of an NCHW batch are contiguous),
-        routed as rg_hip.nn._BatchNorm routes a half: rg_bn_train_*_fused where rg_bn_train_fused_ok says so, else rg_bn_stats +
+        routed as rg_hip.nn.norm._BatchNorm routes a half: rg_bn_train_*_fused where rg_bn_train_fused_ok says so, else rg_bn_stats +
         rg_bn_apply_fwd / rg_bn_bwd_reduce + rg_bn_bwd_apply — the strongest alternative without new kernels.
 The layer carries the ReLU epilogue (as bn1 / bn2 of a Bottleneck do).  Every figure is the MEDIAN of the timed calls, host enqueue
 included; GB/s are algorithmic for the fused layer (forward: x read, y written; backward: x, dy, y read, dx written)."""
