@@ -356,8 +356,12 @@ int rg_segment_mean(const float* x, const void* order, const void* offsets, floa
  *                           R(i, kf) united with every R(c, kh), c in R(i, kf), that has more than 2/3 of its members in
  *                           R(i, kf); sorted, unique; counts[i] is the full size (at most kf * (kh + 1); entries beyond cap
  *                           are dropped, so a count above cap asks for a second call)
- *   rg_rerank_weights_feat  w[i][e] = softmax_e(-(2 - 2 x_i . x_e)) over the row's set, x [N][D]
- *   rg_rerank_weights_dist  w[i][e] = exp(-orig[i][e]) / sum_e, orig [N][N]
+ *   rg_rerank_weights_feat  w[i][e] = softmax_e(-(2 - 2 x_i . x_e)) over the first min(counts[i], cap) entries of the row's
+ *                           set, x [N][D], the maximum subtracted (rows need not be normalised); w[i][min(counts[i], cap):]
+ *                           is not written.  A set entry outside [0, N) gets the weight 0 exactly; a set of ONLY such
+ *                           entries has no maximum and comes back NaN throughout (both forms)
+ *   rg_rerank_weights_dist  w[i][e] = exp(-orig[i][e]) / sum_e, orig [N][N].  No maximum is subtracted: the domain is
+ *                           exp(-orig[i][e]) normal in fp32 (orig below 87; rg_rerank_orig_dist gives [0, 1])
  *   rg_rerank_qe_count      local query expansion, row i = mean of the rows rank[i][:k2] (rank NULL: k2 == 1, the row
  *                           itself): rowcnt[i] = columns of the union, rowptr = their exclusive prefix sum
  *   rg_rerank_qe_fill       the CSR rows: columns ascending, terms added in rank order, divided by k2
@@ -366,7 +370,9 @@ int rg_segment_mean(const float* x, const void* order, const void* offsets, floa
  *                           ascending order, rows i < rows, columns col_off <= j < N, out [rows][N - col_off]; orig != NULL:
  *                           (1 - lambda) * that + lambda * orig[i][j]; clamp != 0: negative results become 0.  chunk = columns
  *                           accumulated per workgroup (<= 16384; 0 = automatic), any value gives the same bits
- *   rg_rerank_orig_dist     orig = transpose(A^2 / max(A^2, axis 0)), A = [[q_q, q_g], [q_g^T, g_g]] (colmax: N floats of scratch) */
+ *   rg_rerank_orig_dist     orig = transpose(A^2 / max(A^2, axis 0)), A = [[q_q, q_g], [q_g^T, g_g]] (colmax: N floats of
+ *                           scratch).  An all-zero column c of A gives 0 / 0: row c of orig is NaN, as the reference's numpy
+ *                           expression gives it */
 int rg_rerank_expand(const int* rank, int N, int R, int kf, int kh, int* sets, int* counts, int cap, rg_stream_t stream);
 int rg_rerank_weights_feat(const float* x, int N, int D, const int* sets, const int* counts, int cap, float* w,
                            rg_stream_t stream);
