@@ -21,13 +21,9 @@ import os
 import numpy as np
 import torch
 
-from rg_hip import ops
+from rg_hip import ops, search
 
 __all__ = ['cmc', 'mean_ap']
-
-
-def _device():
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 def _dist_on_device(distmat):
@@ -38,7 +34,7 @@ def _dist_on_device(distmat):
     if t.dtype not in (torch.float32, torch.float64):
         t = t.float() if t.dtype in (torch.float16, torch.bfloat16) else t.double()
     if not t.is_cuda:
-        t = t.to(_device())
+        t = t.to(search.device())
     return t.contiguous()
 
 

@@ -13,11 +13,7 @@ from __future__ import print_function, absolute_import
 
 import torch
 
-from rg_hip import ops
-
-
-def _device():
-    return torch.device("cuda", torch.cuda.current_device())
+from rg_hip import search
 
 
 def _to_torch(x):
@@ -25,45 +21,24 @@ def _to_torch(x):
 
 
 def extract_cnn_feature(model, inputs):
-    inputs = _to_torch(inputs).to(_device(), non_blocking=True)
+    inputs = _to_torch(inputs).to(search.device(), non_blocking=True)
     with torch.no_grad():
         outputs = model(inputs)
     return outputs.data.cpu()
 
 
 def extract_all_feature(model, inputs):
-    inputs = _to_torch(inputs).to(_device(), non_blocking=True)
+    inputs = _to_torch(inputs).to(search.device(), non_blocking=True)
     with torch.no_grad():
         outputs, extra_outputs = model(inputs, test_all=True)
     return outputs.data.cpu(), extra_outputs.data.cpu()
 
 
-def _dist_block(x, y, xx_scale, with_y_norm):
-    """[m, n] block: xx_scale * |x_i|^2 (+ |y_j|^2) - 2 x_i . y_j — the GEMM with -2 folded into the MFMA epilogue."""
-    n = y.shape[0]
-    minus2 = ops.fill_(torch.empty(n, dtype=torch.float32, device=x.device), -2.0)
-    yy = ops.row_sqsum(y) if with_y_norm else None
-    d = ops.conv2d_fwd(x.view(x.shape[0], x.shape[1], 1, 1), y.view(n, y.shape[1], 1, 1), scale=minus2, shift=yy)
-    d = d.view(x.shape[0], n)
-    return ops.add_outer_terms(d, rowv=ops.row_sqsum(x), colv=None, alpha=1.0, a=xx_scale)
-
-
 def pairwise_distance(features, query=None, gallery=None, return_device=False):
     """return_device=True: the distance matrix (and, with query / gallery, the two feature blocks) stay device tensors"""
-    dev = _device()
+    dist_m, x, y, xd, yd = search.pairwise(features, query, gallery)
     if query is None and gallery is None:
-        n = len(features)
-        x = torch.cat(list(features.values())).view(n, -1).float().to(dev).contiguous()
-        # 2 |x_i|^2 - 2 x_i . x_j  (the reference's expression for the self-distance matrix, :71-77)
-        d = _dist_block(x, x, 2.0, False)
-        return d if return_device else d.cpu()
-    x = torch.cat([features[f].unsqueeze(0) for f, _, _ in query], 0)
-    y = torch.cat([features[f].unsqueeze(0) for f, _, _ in gallery], 0)
-    m, n = x.size(0), y.size(0)
-    x = x.view(m, -1)
-    y = y.view(n, -1)
-    xd, yd = x.float().to(dev).contiguous(), y.float().to(dev).contiguous()
-    dist_m = _dist_block(xd, yd, 1.0, True)
+        return dist_m if return_device else dist_m.cpu()
     if return_device:
         return dist_m, xd, yd
     return dist_m.cpu(), x.numpy(), y.numpy()
@@ -96,7 +71,7 @@ def extract_features_device(model, data_loader, print_freq=50):
     model.eval()
     batch_time, data_time = AverageMeter(), AverageMeter()
     blocks, index, labels = [], OrderedDict(), OrderedDict()
-    dev = _device()
+    dev = search.device()
     end = time.time()
     with torch.no_grad():
         for i, (imgs, fnames, pids, _, _) in enumerate(data_loader):
@@ -121,7 +96,7 @@ def extract_features_device(model, data_loader, print_freq=50):
 
 def pairwise_distance_device(features, query, gallery):
     """[len(query), len(gallery)] squared distances of a DeviceFeatures, on the device"""
-    return _dist_block(features.rows(query), features.rows(gallery), 1.0, True)
+    return search.dist_block(features.rows(query), features.rows(gallery), 1.0, True)
 
 
 def evaluate_all_device(distmat, query=None, gallery=None,

@@ -4,7 +4,7 @@ from __future__ import absolute_import
 
 import torch
 
-from rg_hip import ops
+from rg_hip import ops, search
 
 __all__ = ["label_generator_kmeans"]
 
@@ -15,13 +15,9 @@ def label_generator_kmeans(features, num_classes=500, cuda=True, *, niter=300, s
     device tensor, or a numpy array); with return_device=True labels and centers are device tensors.  `cuda` is accepted and
     ignored: there is no CPU path.  init_centroids [num_classes, D] warm-starts from given centres."""
     assert num_classes, "num_classes for kmeans is null"
-    if not torch.cuda.is_available():
-        raise RuntimeError("label_generator_kmeans: the features must live on the GPU; the HIP path has no CPU fallback")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    x = features if torch.is_tensor(features) else torch.as_tensor(features)
-    x = x.float().to(dev).contiguous()
+    x = search.to_device(features, "label_generator_kmeans: features", refuse_without_gpu=True)
     if init_centroids is not None:
-        init_centroids = torch.as_tensor(init_centroids).float().to(dev).contiguous()
+        init_centroids = search.to_device(init_centroids, "label_generator_kmeans: init_centroids")
     labels, centers, _ = ops.kmeans(x, int(num_classes), niter=niter, seed=seed, init_centroids=init_centroids)
     if return_device:
         return labels, centers, num_classes, None

@@ -21,7 +21,7 @@ import torch
 from rg_hip.tape import backward as _backward
 import torch.nn as nn
 
-from rg_hip import functional as RF
+from rg_hip import functional as RF, search
 from rg_hip.nn import invalidate_folds
 from rg_hip.parallel import GradReducer, attach_stage_hooks
 
@@ -32,10 +32,6 @@ try:                                    # optional observability, never on the h
     import wandb as _wandb
 except Exception:                       # pragma: no cover
     _wandb = None
-
-
-def _device():
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 def _first(out):
@@ -131,7 +127,7 @@ class ClusterContrastTrainer(object):
 
     def _parse_data(self, inputs):
         imgs, _, pids, _, indexes = inputs
-        dev = _device()
+        dev = search.device()
         return imgs.to(dev, non_blocking=True), pids.to(dev, non_blocking=True), indexes.to(dev, non_blocking=True)
 
     def _forward(self, inputs):
@@ -393,7 +389,7 @@ class ClusterContrastWithGANTrainer(object):
 
     def _parse_data(self, inputs):
         imgs, _, pids, _, indexes = inputs
-        dev = _device()
+        dev = search.device()
         return imgs.to(dev, non_blocking=True), pids.to(dev, non_blocking=True), indexes.to(dev, non_blocking=True)
 
     def _forward(self, inputs, fuse=True):

@@ -27,11 +27,7 @@ from __future__ import absolute_import
 import numpy as np
 import torch
 
-from rg_hip import ops
-
-
-def _device():
-    return torch.device("cuda", torch.cuda.current_device())
+from rg_hip import ops, search
 
 
 class DBSCAN(object):
@@ -66,7 +62,7 @@ class DBSCAN(object):
         if sample_weight is not None:
             raise ValueError("DBSCAN: sample_weight is not implemented")
         X = self._validated(X)
-        d = X.detach().to(_device()).contiguous()
+        d = X.detach().to(search.device()).contiguous()
         if self.check_symmetric:
             bad = ops.dbscan_asymmetry(d)
             if bad:

@@ -23,15 +23,8 @@ from __future__ import absolute_import, print_function
 import time
 
 import numpy as np
-import torch
 
-from rg_hip import ops
-
-_BLOCK_ROWS = 2048
-
-
-def _device():
-    return torch.device("cuda", torch.cuda.current_device())
+from rg_hip import ops, search
 
 
 def k_reciprocal_neigh(initial_rank, i, k1):
@@ -47,15 +40,12 @@ def half_k(k1):
 
 def l2_rank(x, k):
     """int32 [N, k]: the k nearest rows of x [N, D] (device, fp32) by squared L2 distance, ascending, ties by lower index"""
-    n = x.shape[0]
     sq = ops.row_sqsum(x)
-    rank = torch.empty((n, k), dtype=torch.int32, device=x.device)
-    for r0 in range(0, n, _BLOCK_ROWS):
-        r1 = min(n, r0 + _BLOCK_ROWS)
-        block = ops.linear_fwd(x[r0:r1], x)                              # [rows, n] inner products
-        ops.add_outer_terms(block, None, sq, alpha=2.0, b=-1.0)          # 2 x_i . x_j - |x_j|^2 = |x_i|^2 - d^2
-        rank[r0:r1] = ops.topk_rows(block, k)[0]
-    return rank
+
+    def score_block(r0, r1):
+        block = ops.linear_fwd(x[r0:r1], x)                                      # [rows, n] inner products
+        return ops.add_outer_terms(block, None, sq, alpha=2.0, b=-1.0)           # 2 x_i . x_j - |x_j|^2 = |x_i|^2 - d^2
+    return search.blocked_topk(x.shape[0], k, score_block)
 
 
 def compute_jaccard_distance(target_features, k1=20, k2=6, print_flag=True, search_option=0, use_float16=False, chunk=0,
@@ -69,17 +59,14 @@ def compute_jaccard_distance(target_features, k1=20, k2=6, print_flag=True, sear
     end = time.time()
     if print_flag:
         print('Computing jaccard distance...')
-    if not torch.is_tensor(target_features):
-        target_features = torch.as_tensor(np.ascontiguousarray(target_features, dtype=np.float32))
-    if target_features.dim() != 2:
-        raise ValueError("compute_jaccard_distance: target_features must be [N, D], got %s" % (tuple(target_features.shape),))
+    target_features = search.as_matrix(target_features, "compute_jaccard_distance: target_features")
     N = target_features.size(0)
     k1, k2 = int(k1), int(k2)
     if not 1 <= k1 < N:
         raise ValueError("compute_jaccard_distance: need 1 <= k1 < N, got k1=%d, N=%d" % (k1, N))
     if not 1 <= k2 <= k1:
         raise ValueError("compute_jaccard_distance: need 1 <= k2 <= k1, got k2=%d, k1=%d" % (k2, k1))
-    x = target_features.detach().float().to(_device()).contiguous()
+    x = target_features.to(search.device()).contiguous()
     rank = l2_rank(x, k1)              # the reference searches k1 neighbours: its slice [:k1+1] has k1 entries
     res = ops.rerank_from_rank(rank, k1, min(half_k(k1) + 1, k1), k2, x=x, clamp=True, chunk=chunk, debug=debug)
     out = res[0] if debug else res

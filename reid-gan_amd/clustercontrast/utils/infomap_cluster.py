@@ -28,13 +28,7 @@ import collections
 import numpy as np
 import torch
 
-from rg_hip import ops
-
-_BLOCK_ROWS = 2048
-
-
-def _device():
-    return torch.device("cuda", torch.cuda.current_device())
+from rg_hip import ops, search
 
 
 class knn_faiss(object):
@@ -42,18 +36,9 @@ class knn_faiss(object):
 
     def __init__(self, feats, k, knn_method='faiss-cpu', verbose=True):
         self.verbose = verbose
-        dev = _device()
-        x = torch.as_tensor(np.ascontiguousarray(feats, dtype=np.float32)) if not torch.is_tensor(feats) else feats.float()
-        x = x.to(dev).contiguous()
-        n = x.shape[0]
-        nbrs = torch.empty((n, k), dtype=torch.int32, device=dev)
-        sims = torch.empty((n, k), dtype=torch.float32, device=dev)
-        for r0 in range(0, n, _BLOCK_ROWS):
-            r1 = min(n, r0 + _BLOCK_ROWS)
-            block = ops.linear_fwd(x[r0:r1], x)                  # [rows, n] inner products
-            i, v = ops.topk_rows(block, k)
-            nbrs[r0:r1], sims[r0:r1] = i, v
-        self.nbrs, self.sims = nbrs, sims
+        x = search.to_device(feats, "knn_faiss: feats")
+        # [rows, n] inner products per block
+        self.nbrs, self.sims = search.blocked_topk(x.shape[0], k, lambda r0, r1: ops.linear_fwd(x[r0:r1], x), want_values=True)
         self._knns = None
 
     @property
@@ -124,10 +109,8 @@ def generate_cluster_features(labels, features):
         raise ValueError("generate_cluster_features: every sample is an outlier")
     order = [i for kk in keys for i in groups[kk]]
     offsets = np.cumsum([0] + [len(groups[kk]) for kk in keys])
-    dev = _device()
-    x = features if torch.is_tensor(features) else torch.stack(list(features), dim=0)
-    x = x.float().to(dev).contiguous()
-    return ops.segment_mean(x, torch.tensor(order, dtype=torch.int64).to(dev), torch.tensor(offsets, dtype=torch.int64).to(dev))
+    x = search.to_device(features, "generate_cluster_features: features", rows_ok=True)
+    return ops.segment_mean(x, torch.tensor(order, dtype=torch.int64).to(x.device), torch.tensor(offsets, dtype=torch.int64).to(x.device))
 
 
 @torch.no_grad()
@@ -138,19 +121,14 @@ def generate_cluster_features_device(labels, features):
     [number of distinct labels, D]."""
     if not torch.is_tensor(labels) or not labels.is_cuda or labels.dtype != torch.int64 or labels.dim() != 1:
         raise TypeError("generate_cluster_features_device: labels must be a 1-D int64 device tensor")
-    x = features if torch.is_tensor(features) else torch.stack(list(features), dim=0)
-    x = x.float().to(labels.device).contiguous()
-    if x.dim() != 2 or x.shape[0] != labels.numel():
+    x = search.as_matrix(features, "generate_cluster_features_device: features", rows_ok=True).to(labels.device).contiguous()
+    if x.shape[0] != labels.numel():
         raise ValueError("generate_cluster_features_device: features %s do not match %d labels" % (tuple(x.shape), labels.numel()))
     keep = torch.nonzero(labels != -1).flatten()                  # ascending sample index
     if keep.numel() == 0:
         raise ValueError("generate_cluster_features_device: every sample is an outlier")
-    sorted_labels, perm = torch.sort(labels[keep], stable=True)
-    order = keep[perm].contiguous()
-    _, sizes = torch.unique_consecutive(sorted_labels, return_counts=True)
-    offsets = torch.zeros(sizes.numel() + 1, dtype=torch.int64, device=labels.device)
-    offsets[1:] = torch.cumsum(sizes, dim=0)
-    return ops.segment_mean(x, order, offsets)
+    _, perm, offsets = ops.sorted_segments(labels[keep], ptr_dtype=torch.int64)
+    return ops.segment_mean(x, keep[perm].contiguous(), offsets)
 
 
 def _check_min_sim(min_sim, who):
@@ -183,7 +161,7 @@ def _table_on_device(nbrs, dists, who):
     if not (1 <= nbrs.shape[0] <= ops.INFOMAP_MAX_N and 1 <= nbrs.shape[1] <= ops.INFOMAP_MAX_K):
         raise ValueError("%s needs 1 <= N <= %d and 1 <= k <= %d, got N=%d k=%d"
                          % (who, ops.INFOMAP_MAX_N, ops.INFOMAP_MAX_K, nbrs.shape[0], nbrs.shape[1]))
-    dev = _device()
+    dev = search.device()
     return nbrs.to(dev), dists.to(dev)
 
 

@@ -21,9 +21,22 @@ import time
 
 import torch
 
-from rg_hip import ops
+from rg_hip import ops, search
 from .faiss_rerank import compute_jaccard_distance
 from .infomap_cluster import cluster_by_infomap, generate_cluster_features_device, get_dist_nbr
+
+
+def _finish(labels, x, any_cluster, print_flag, line, end):
+    """the shared epilogue: (labels as numpy, per-cluster means of x [N, D] in ascending label order — an empty [0, D] tensor
+    without a cluster); `line(pseudo_labels, cluster_features)` is the recipe's progress line without its time"""
+    if any_cluster:
+        cluster_features = generate_cluster_features_device(labels, x)
+    else:
+        cluster_features = torch.empty((0, x.shape[1]), dtype=torch.float32, device=labels.device)
+    pseudo_labels = labels.cpu().numpy()
+    if print_flag:
+        print("{}, time cost: {}".format(line(pseudo_labels, cluster_features), time.time() - end))
+    return pseudo_labels, cluster_features
 
 
 @torch.no_grad()
@@ -39,15 +52,9 @@ def dbscan_pseudo_labels(features, k1=30, k2=6, eps=0.6, min_samples=4, print_fl
     dist = compute_jaccard_distance(features, k1=k1, k2=k2, print_flag=print_flag, return_device=True)
     labels, num_cluster = ops.dbscan(dist, float(eps), int(min_samples))
     del dist
-    x = features if torch.is_tensor(features) else torch.as_tensor(features)
-    if num_cluster:
-        cluster_features = generate_cluster_features_device(labels, x)
-    else:
-        cluster_features = torch.empty((0, x.shape[1]), dtype=torch.float32, device=labels.device)
-    pseudo_labels = labels.cpu().numpy()
-    if print_flag:
-        print("DBSCAN pseudo labels: {} clusters, {} outliers, time cost: {}".format(
-            num_cluster, int((pseudo_labels == -1).sum()), time.time() - end))
+    pseudo_labels, cluster_features = _finish(
+        labels, search.as_matrix(features, "dbscan_pseudo_labels: features"), num_cluster, print_flag,
+        lambda pl, cf: "DBSCAN pseudo labels: {} clusters, {} outliers".format(num_cluster, int((pl == -1).sum())), end)
     return pseudo_labels, num_cluster, cluster_features
 
 
@@ -59,22 +66,14 @@ def infomap_pseudo_labels(features, k=15, min_sim=0.5, cluster_num=4, print_flag
     mean of the normalised rows of every cluster in ascending label order (an empty [0, D] tensor without a cluster).  Only
     the N labels are copied out.  The defaults are the scripts' --k1 15 --eps 0.5 --k2 4."""
     end = time.time()
-    x = features if torch.is_tensor(features) else torch.as_tensor(features)
-    if x.dim() != 2:
-        raise ValueError("infomap_pseudo_labels: features must be [N, D], got shape %s" % (tuple(x.shape),))
-    if not torch.cuda.is_available():
-        raise RuntimeError("infomap_pseudo_labels: features must live on the GPU; the HIP path has no CPU fallback")
-    x = torch.nn.functional.normalize(x.float().to(torch.device("cuda", torch.cuda.current_device())), dim=1).contiguous()
+    x = search.to_device(features, "infomap_pseudo_labels: features", refuse_without_gpu=True)
+    x = torch.nn.functional.normalize(x, dim=1).contiguous()
     dists, nbrs = get_dist_nbr(x, k=int(k), knn_method='faiss-gpu', return_device=True)
     labels, info = cluster_by_infomap(nbrs, dists, min_sim=min_sim, cluster_num=cluster_num, return_device=True, return_info=True)
-    if info["n_clusters"]:
-        cluster_features = generate_cluster_features_device(labels, x)
-    else:
-        cluster_features = torch.empty((0, x.shape[1]), dtype=torch.float32, device=labels.device)
-    pseudo_labels = labels.cpu().numpy()
-    if print_flag:
-        print("Infomap pseudo labels: {} clusters, {} outliers, codelength {:.4f} bits, time cost: {}".format(
-            info["n_clusters"], int((pseudo_labels == -1).sum()), info["codelength"], time.time() - end))
+    pseudo_labels, cluster_features = _finish(
+        labels, x, info["n_clusters"], print_flag,
+        lambda pl, cf: "Infomap pseudo labels: {} clusters, {} outliers, codelength {:.4f} bits".format(
+            info["n_clusters"], int((pl == -1).sum()), info["codelength"]), end)
     return pseudo_labels, cluster_features, info
 
 
@@ -86,16 +85,10 @@ def kmeans_pseudo_labels(features, num_classes=500, niter=300, print_flag=False)
     label that occurs, in ascending label order: C == num_classes unless the final assignment leaves a centroid without a
     row.  Only the N labels are copied out."""
     end = time.time()
-    x = features if torch.is_tensor(features) else torch.as_tensor(features)
-    if x.dim() != 2:
-        raise ValueError("kmeans_pseudo_labels: features must be [N, D], got shape %s" % (tuple(x.shape),))
-    if not torch.cuda.is_available():
-        raise RuntimeError("kmeans_pseudo_labels: features must live on the GPU; the HIP path has no CPU fallback")
-    x = x.float().to(torch.device("cuda", torch.cuda.current_device())).contiguous()
+    x = search.to_device(features, "kmeans_pseudo_labels: features", refuse_without_gpu=True)
     labels, _, info = ops.kmeans(x, int(num_classes), niter=int(niter))
-    cluster_features = generate_cluster_features_device(labels, x)
-    pseudo_labels = labels.cpu().numpy()
-    if print_flag:
-        print("k-means pseudo labels: {} clusters, {} iterations, objective {:.4f}, time cost: {}".format(
-            cluster_features.shape[0], info["iterations"], info["obj"][-1] if info["obj"] else float("nan"), time.time() - end))
+    pseudo_labels, cluster_features = _finish(
+        labels, x, True, print_flag,
+        lambda pl, cf: "k-means pseudo labels: {} clusters, {} iterations, objective {:.4f}".format(
+            cf.shape[0], info["iterations"], info["obj"][-1] if info["obj"] else float("nan")), end)
     return pseudo_labels, cluster_features, info

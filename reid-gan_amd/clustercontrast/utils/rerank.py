@@ -15,33 +15,18 @@ Inputs are numpy arrays or tensors (any float type; computed in fp32 like the re
 """
 from __future__ import absolute_import, division, print_function
 
-import numpy as np
-import torch
-
-from rg_hip import ops
+from rg_hip import ops, search
 
 from .faiss_rerank import half_k
 
 __all__ = ['re_ranking']
 
-_BLOCK_ROWS = 2048
-
-
-def _device():
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _as_f32(a, name):
-    t = a if torch.is_tensor(a) else torch.as_tensor(np.ascontiguousarray(a))
-    if t.dim() != 2:
-        raise ValueError("re_ranking: %s must be a matrix, got shape %s" % (name, tuple(t.shape)))
-    return t.detach().float()
-
 
 def re_ranking(q_g_dist, q_q_dist, g_g_dist, k1=20, k2=6, lambda_value=0.3, chunk=0, debug=False, return_device=False):
     """numpy [Q, G] float32: (1 - lambda) * Jaccard distance + lambda * normalised original distance
     (return_device=True: the same matrix as a device tensor, not copied to the host)"""
-    q_g, q_q, g_g = _as_f32(q_g_dist, "q_g_dist"), _as_f32(q_q_dist, "q_q_dist"), _as_f32(g_g_dist, "g_g_dist")
+    q_g, q_q, g_g = (search.as_matrix(a, "re_ranking: " + name)
+                     for a, name in ((q_g_dist, "q_g_dist"), (q_q_dist, "q_q_dist"), (g_g_dist, "g_g_dist")))
     Q, G = q_g.shape
     if tuple(q_q.shape) != (Q, Q) or tuple(g_g.shape) != (G, G):
         raise ValueError("re_ranking: q_g_dist %s needs q_q_dist [%d, %d] and g_g_dist [%d, %d], got %s and %s"
@@ -52,14 +37,11 @@ def re_ranking(q_g_dist, q_q_dist, g_g_dist, k1=20, k2=6, lambda_value=0.3, chun
         raise ValueError("re_ranking: need 1 <= k1 < Q + G, got k1=%d, Q + G=%d" % (k1, N))
     if not 1 <= k2 <= k1:
         raise ValueError("re_ranking: need 1 <= k2 <= k1, got k2=%d, k1=%d" % (k2, k1))
-    dev = _device()
+    dev = search.device()
     orig = ops.rerank_orig_dist(q_g.to(dev).contiguous(), q_q.to(dev).contiguous(), g_g.to(dev).contiguous())
     R = k1 + 1                                      # the only columns of the argsort that are read (k2 <= k1)
-    rank = torch.empty((N, R), dtype=torch.int32, device=dev)
-    for r0 in range(0, N, _BLOCK_ROWS):
-        r1 = min(N, r0 + _BLOCK_ROWS)
-        neg = ops.add_outer_terms(orig[r0:r1].clone(), alpha=-1.0)       # top-k of -d = the k smallest d
-        rank[r0:r1] = ops.topk_rows(neg, R)[0]
+    # top-k of -d = the k smallest d
+    rank = search.blocked_topk(N, R, lambda r0, r1: ops.add_outer_terms(orig[r0:r1].clone(), alpha=-1.0))
     res = ops.rerank_from_rank(rank, k1 + 1, half_k(k1) + 1, k2, orig=orig, rows=Q, col_off=Q, lambda_value=lambda_value,
                                clamp=False, chunk=chunk, debug=debug)
     out = res[0] if debug else res

@@ -16,34 +16,19 @@ from __future__ import print_function, absolute_import
 import numpy as np
 import torch
 
-from clustercontrast.evaluators import _dist_block
-from rg_hip import ops
-
-
-def _device():
-    return torch.device("cuda", torch.cuda.current_device())
+from rg_hip import ops, search
 
 
 def pairwise_distance(features, query=None, gallery=None, metric=None):
     if metric is not None:
         raise NotImplementedError("pairwise_distance: learned metrics (metric.transform) are not on the GAN path")
-    dev = _device()
-    if query is None and gallery is None:
-        n = len(features)
-        x = torch.cat(list(features.values())).view(n, -1).float().to(dev).contiguous()
-        return _dist_block(x, x, 2.0, False).cpu()
-    x = torch.cat([features[f].unsqueeze(0) for f, _, _ in query], 0)
-    y = torch.cat([features[f].unsqueeze(0) for f, _, _ in gallery], 0)
-    xd = x.view(x.size(0), -1).float().to(dev).contiguous()
-    yd = y.view(y.size(0), -1).float().to(dev).contiguous()
-    return _dist_block(xd, yd, 1.0, True).cpu()
+    return search.pairwise(features, query, gallery)[0].cpu()
 
 
 def rank_topk(distmat, k):
     """indices [Q, k] of the k smallest distances per row, ascending, ties by lower column (device top-k of -dist)"""
-    d = torch.as_tensor(distmat, dtype=torch.float32).to(_device()).contiguous()
-    idx, _ = ops.topk_rows(ops.scale(d, -1.0), int(k))
-    return idx.long()
+    d = search.to_device(distmat, "rank_topk: distmat")
+    return search.blocked_topk(d.shape[0], int(k), lambda r0, r1: ops.scale(d[r0:r1], -1.0)).long()
 
 
 def extract_embeddings(model, features, alpha, query=None, topk_gallery=None, rerank_topk=0, print_freq=500,
@@ -52,16 +37,14 @@ def extract_embeddings(model, features, alpha, query=None, topk_gallery=None, re
     (`topk_gallery`: per query, the list of gallery (fname, pid, cam) triples); `topk_indices` [Q, k] + `gallery` is the
     device form used by CascadeEvaluator (no per-query Python lists)."""
     model.eval()
-    dev = _device()
-    probe = torch.cat([features[f].unsqueeze(0) for f, _, _ in query], 0).float()
+    probe = search.to_device(search.stack_rows(features, query), "extract_embeddings: query features")
     Q = probe.shape[0]
     if topk_indices is not None:
-        gal = torch.cat([features[f].unsqueeze(0) for f, _, _ in gallery], 0).float().to(dev)
-        idx = topk_indices.to(dev).reshape(-1)
-        x2 = gal.index_select(0, idx)
+        gal = search.to_device(search.stack_rows(features, gallery), "extract_embeddings: gallery features")
+        x2 = gal.index_select(0, topk_indices.to(gal.device).reshape(-1))
     else:
-        x2 = torch.cat([features[f].unsqueeze(0) for i in range(Q) for f, _, _ in topk_gallery[i]], 0).float().to(dev)
-    probe = probe.to(dev)
+        x2 = search.to_device(search.stack_rows(features, [e for i in range(Q) for e in topk_gallery[i]]),
+                              "extract_embeddings: gallery features")
     x1 = probe.view(Q, 1, -1).expand(Q, rerank_topk, probe.shape[1]).reshape(Q * rerank_topk, -1).contiguous()
     with torch.no_grad():
         score = model(x1, x2.contiguous())

@@ -6,7 +6,8 @@ otherwise (there is deliberately no CPU path).
 This file is the namespace and nothing else: `ops.<name>` for every wrapper, defined in the submodule of the kernel-library
 unit(s) it calls.
 
-    _base      library handle, ACT_* codes, device binding, the validators (_chk, _dense, _chk_rr), workspace, split-K counters
+    _base      library handle, ACT_* codes, device binding, the validators (_chk, _dense, _chk_rr), the two-pass list total,
+               workspace, split-K counters
     streams    concurrent_stream and its hardware-queue probe, the weight-gradient side-stream session (side_*)
     conv       csrc/conv_*.hip: conv2d_fwd / dgrad / wgrad, linear_*
     norm       csrc/norm_*.hip: bn_*, instnorm_*, ibn_*, dsbn_*, the folded-BatchNorm helpers, channel_sum
@@ -14,7 +15,8 @@ unit(s) it calls.
     gan        csrc/gan_extra.hip: avgpool2d, reflection padding, spectral normalisation
     pool       csrc/pool.hip, part_head.hip: maxpool, global average, GeM, part pooling, the multi-part head
     loss       csrc/loss.hip
-    retrieval  csrc/cm.hip, retrieval.hip, rerank.hip, rank_eval.hip: cluster memory, kNN helpers, re-ranking, CMC / mAP
+    retrieval  csrc/cm.hip, retrieval.hip, rerank.hip, rank_eval.hip: cluster memory, kNN helpers, sort segments and label
+               compaction (torch), re-ranking, CMC / mAP
     dbscan     csrc/dbscan.hip
     infomap    csrc/infomap.hip: the wrappers and the host-driven search
     kmeans     csrc/kmeans.hip: assign / tally / update / split and the host loop over them
@@ -54,9 +56,9 @@ from .pool import (maxpool2d_fwd, maxpool2d_bwd, global_avgpool_fwd, global_avgp
 from .loss import (sigmoid_bce_fwd, sigmoid_bce_bwd, mse_const_fwd, mse_const_bwd, affine_relu_mean_fwd, affine_relu_mean_bwd,
                    grad_penalty_rows, l1_fwd, l1_bwd, l1_rows_fwd, l1_rows_bwd, mse_const_rows_fwd, mse_const_rows_bwd,
                    softmax_ce_fwd, softmax_ce_bwd, softmax_ce_ext_fwd, softmax_ce_ext_bwd, weighted_sum_fwd, weighted_sum_bwd)
-from .retrieval import (cm_update, normalize_listed_rows, topk_rows, row_sqsum, add_outer_terms, segment_mean, rerank_expand,
-                        rerank_weights, rerank_query_expand, rerank_columns, rerank_jaccard, rerank_orig_dist, rerank_from_rank,
-                        rank_eval)
+from .retrieval import (cm_update, normalize_listed_rows, topk_rows, row_sqsum, add_outer_terms, segment_mean, sorted_segments,
+                        compact_labels, rerank_expand, rerank_weights, rerank_query_expand, rerank_columns, rerank_jaccard,
+                        rerank_orig_dist, rerank_from_rank, rank_eval)
 from .dbscan import dbscan_count, dbscan_fill, dbscan_neighbors, dbscan_components, dbscan_labels, dbscan_asymmetry, dbscan
 from .infomap import (INFOMAP_MAX_N, INFOMAP_MAX_K, INFOMAP_FLOW_MAX_ITERS, INFOMAP_FLOW_BATCH, INFOMAP_SWEEP_CAP,
                       INFOMAP_LEVEL_CAP, INFOMAP_ROUND_CAP, infomap_links, infomap_flow, infomap_codelength, infomap_search,
@@ -75,7 +77,7 @@ from .profile import _PROFILING
 from .infomap import _infomap_leaf_units, _infomap_totals, _infomap_codelength_of
 
 # ---- the other module-level underscore names of the former single file: nothing outside reads them today, they stay reachable ------
-from ._base import _DEV, _bind_device, _dense, _chk_rr, _nchw, _same_size, _eps32, _SPLITK_INKERNEL, _Workspace, _ws
+from ._base import _DEV, _bind_device, _dense, _chk_rr, _nchw, _same_size, _eps32, _list_total, _SPLITK_INKERNEL, _Workspace, _ws
 from .streams import _HANDED, _PROBE_US, _share_a_queue, _INLINE_SIDE, _SideSession, _SIDE_MIN_US, _GRAPH_SIDE_MIN_US
 from .norm import _BN_FUSED
 from .eltwise import _CONST_FILL, _CLOCK

@@ -115,6 +115,16 @@ def _eps32(eps):
     return float(torch.tensor(float(eps), dtype=torch.float32))
 
 
+def _list_total(rowptr, cnt, n, worst_case, who):
+    """the one readback between the two passes of a list builder (count + scan, then fill): the length of the list, rowptr[n]
+    of the int32 exclusive prefix sum of cnt int32 [n].  Where the worst case could wrap that sum it is the int64 sum of cnt
+    instead.  Refused outside [0, 2^31): the fill pass indexes with the int32 row pointers."""
+    total = int(cnt.sum(dtype=torch.int64).item()) if worst_case >= 2 ** 31 else int(rowptr[n].item())
+    if not 0 <= total < 2 ** 31:
+        raise RuntimeError("rg_hip: %s: %d entries do not fit the int32 row pointers" % (who, total))
+    return total
+
+
 _SPLITK_INKERNEL = os.environ.get("RG_SPLITK_INKERNEL", "0") not in ("", "0")
 
 

@@ -3,7 +3,7 @@ from __future__ import absolute_import
 
 import torch
 
-from ._base import _chk_rr, _eps32, _p, _stream, lib
+from ._base import _chk_rr, _eps32, _list_total, _p, _stream, lib
 
 
 # ------------------------------------------------------------------------------------------------
@@ -63,11 +63,7 @@ def dbscan_neighbors(d, eps, min_samples):
         raise ValueError("rg_hip: dbscan needs min_samples >= 1, got %d" % int(min_samples))
     N = d.shape[0]
     cnt, rowptr = dbscan_count(d, eps)
-    nnz = int(rowptr[N].item())
-    if N * N >= 2 ** 31:                 # the int32 prefix sum can wrap only beyond 46 340 rows
-        nnz = int(cnt.sum(dtype=torch.int64).item())
-    if nnz < 0 or nnz >= 2 ** 31:
-        raise RuntimeError("rg_hip: dbscan_neighbors: %d neighbours do not fit the int32 row pointers" % nnz)
+    nnz = _list_total(rowptr, cnt, N, N * N, "dbscan_neighbors")      # the int32 prefix sum can wrap only beyond 46 340 rows
     nbr, core = dbscan_fill(d, eps, min_samples, rowptr, nnz)
     return rowptr, nbr, core
 

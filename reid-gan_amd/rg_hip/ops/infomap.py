@@ -3,7 +3,8 @@ from __future__ import absolute_import
 
 import torch
 
-from ._base import _chk_rr, _eps32, _p, _stream, lib
+from ._base import _chk_rr, _eps32, _list_total, _p, _stream, lib
+from .retrieval import compact_labels, sorted_segments
 
 
 # ------------------------------------------------------------------------------------------------
@@ -59,7 +60,7 @@ def infomap_links(nbrs, dists, min_sim):
     cnt = torch.empty((N,), dtype=torch.int32, device=dev)
     rowptr = torch.empty((N + 1,), dtype=torch.int32, device=dev)
     lib.rg_infomap_links_count(_p(nbrs), _p(dists), N, k, thr, _p(cnt), _p(rowptr), _stream())
-    E = int(rowptr[N].item())
+    E = _list_total(rowptr, cnt, N, N * k, "infomap_links")
     src = torch.empty((E,), dtype=torch.int32, device=dev)
     dst = torch.empty((E,), dtype=torch.int32, device=dev)
     w = torch.empty((E,), dtype=torch.float64, device=dev)
@@ -119,12 +120,8 @@ def _infomap_totals(ug, mod):
     """(exit, enter, flow fp64 [U], nunits int32 [U]) of the modules mod int32 [U] (values in [0, U)) of a unit graph, every
     module summed over its units in ascending index (segments of a stable sort)"""
     U, dev = ug["U"], mod.device
-    smod, order = torch.sort(mod, stable=True)
-    _, counts = torch.unique_consecutive(smod, return_counts=True)
-    S = counts.numel()
-    segptr = torch.zeros((S + 1,), dtype=torch.int32, device=dev)
-    segptr[1:] = torch.cumsum(counts, dim=0)
-    order = order.to(torch.int32)
+    _, order, segptr = sorted_segments(mod)
+    S, order = segptr.numel() - 1, order.to(torch.int32)
     xo, xi = torch.empty((U,), dtype=torch.float64, device=dev), torch.empty((U,), dtype=torch.float64, device=dev)
     mexit, menter, mflow = (torch.zeros((U,), dtype=torch.float64, device=dev) for _ in range(3))
     nunits = torch.zeros((U,), dtype=torch.int32, device=dev)
@@ -147,8 +144,7 @@ def infomap_codelength(graph, labels):
         raise RuntimeError("rg_hip: labels must live on the GPU (got %s); the HIP path has no CPU fallback" % (labels.device,))
     if labels.dtype not in (torch.int32, torch.int64) or labels.dim() != 1 or labels.numel() != g["N"]:
         raise ValueError("rg_hip: infomap_codelength: labels must be an int32 / int64 vector of %d entries" % g["N"])
-    _, inv = torch.unique(labels, return_inverse=True)
-    mod = inv.to(torch.int32).contiguous()
+    mod, _ = compact_labels(labels)
     tot = _infomap_totals(_infomap_leaf_units(g), mod)
     out = torch.empty((2,), dtype=torch.float64, device=mod.device)
     _infomap_codelength_of(tot, g["scal"], out)
@@ -208,9 +204,7 @@ def _infomap_aggregate(g, leaf_mod):
     sum of the leaf links between them in ascending link index (segments of a stable sort of the module pairs), unit flow =
     the module's node flow in ascending node index"""
     N, dev = g["N"], leaf_mod.device
-    _, inv = torch.unique(leaf_mod, return_inverse=True)
-    lm = inv.to(torch.int32).contiguous()
-    M = int(lm.max().item()) + 1
+    lm, M = compact_labels(leaf_mod)
     leaf = _infomap_leaf_units(g)
     pu = _infomap_totals(leaf, lm)[2][:M].contiguous()
     ms, md = lm[g["src"].long()].long(), lm[g["dst"].long()].long()
@@ -220,12 +214,8 @@ def _infomap_aggregate(g, leaf_mod):
         return ug, lm
     lists = []
     for a, b in ((ms[cross], md[cross]), (md[cross], ms[cross])):      # out lists by (source, target), in lists by (target, source)
-        skey, perm = torch.sort(a * M + b, stable=True)
-        pairs, counts = torch.unique_consecutive(skey, return_counts=True)
-        S = pairs.numel()
-        segptr = torch.zeros((S + 1,), dtype=torch.int32, device=dev)
-        segptr[1:] = torch.cumsum(counts, dim=0)
-        eidx = cross[perm].to(torch.int32)
+        pairs, perm, segptr = sorted_segments(a * M + b)
+        S, eidx = pairs.numel(), cross[perm].to(torch.int32)
         val = torch.empty((S,), dtype=torch.float64, device=dev)
         lib.rg_infomap_segment_sum(_p(g["q"]), g["E"], _p(eidx), _p(segptr), S, eidx.numel(), _p(val), _stream())
         row = torch.div(pairs, M, rounding_mode="floor")
@@ -261,16 +251,13 @@ def infomap_search(graph):
                 settled = True
                 break
             leaf_mod = mod[leaf_mod.long()].contiguous()
-        _, inv = torch.unique(leaf_mod, return_inverse=True)
-        leaf_mod = inv.to(torch.int32).contiguous()
+        leaf_mod, _ = compact_labels(leaf_mod)
         stats["levels"] += 1
         if not _infomap_level(leaf, leaf_mod, g["scal"], stats) and settled:      # the last coarse level moved nothing either
             converged = True
             break
-    _, inv = torch.unique(leaf_mod, return_inverse=True)
-    leaf_mod = inv.to(torch.int32).contiguous()
+    leaf_mod, stats["n_modules"] = compact_labels(leaf_mod)
     stats["converged"] = converged
-    stats["n_modules"] = int(leaf_mod.max().item()) + 1
     return leaf_mod, stats
 
 

@@ -4,7 +4,7 @@ from __future__ import absolute_import
 
 import torch
 
-from ._base import _chk, _chk_rr, _p, _stream, lib
+from ._base import _chk, _chk_rr, _list_total, _p, _stream, lib
 
 
 # ------------------------------------------------------------------------------------------------
@@ -66,6 +66,23 @@ def segment_mean(x, order, offsets):
     return out
 
 
+def sorted_segments(keys, ptr_dtype=torch.int32):
+    """(uniq, perm, ptr) of a stable sort of the 1-D `keys`: the distinct keys ascending, the sorting permutation (int64: equal
+    keys keep their order, so a segment lists its members in ascending position) and ptr [S + 1] in ptr_dtype, the exclusive
+    prefix sum of the segment sizes: segment s is perm[ptr[s]:ptr[s + 1]].  Pure torch, on the device of `keys`."""
+    skeys, perm = torch.sort(keys, stable=True)
+    uniq, counts = torch.unique_consecutive(skeys, return_counts=True)
+    ptr = torch.zeros((uniq.numel() + 1,), dtype=ptr_dtype, device=keys.device)
+    ptr[1:] = torch.cumsum(counts, dim=0)
+    return uniq, perm, ptr
+
+
+def compact_labels(t):
+    """(inverse int32 contiguous, count): every entry of `t` replaced by the rank of its value among the `count` distinct ones"""
+    uniq, inv = torch.unique(t, return_inverse=True)
+    return inv.to(torch.int32).contiguous(), uniq.numel()
+
+
 # ------------------------------------------------------------------------------------------------
 # k-reciprocal re-ranking (csrc/rerank.hip): sparse encodings as row lists, see include/reidgan_hip.h
 # ------------------------------------------------------------------------------------------------
@@ -124,9 +141,9 @@ def rerank_query_expand(sets, w, counts, rank=None, k2=1):
     rowcnt = torch.empty((N,), dtype=torch.int32, device=sets.device)
     rowptr = torch.empty((N + 1,), dtype=torch.int32, device=sets.device)
     lib.rg_rerank_qe_count(_p(rank), R, k2, N, _p(sets), _p(counts), cap, _p(rowcnt), _p(rowptr), _stream())
-    nnz = int(rowptr[N].item())
-    if nnz <= 0 or nnz >= 2 ** 31:
-        raise RuntimeError("rg_hip: rerank_query_expand: %d non-zeros do not fit the int32 row pointers" % nnz)
+    nnz = _list_total(rowptr, rowcnt, N, N * min(N, k2 * cap), "rerank_query_expand")
+    if nnz == 0:
+        raise RuntimeError("rg_hip: rerank_query_expand: every expanded set is empty")
     cols = torch.empty((nnz,), dtype=torch.int32, device=sets.device)
     vals = torch.empty((nnz,), dtype=torch.float32, device=sets.device)
     lib.rg_rerank_qe_fill(_p(rank), R, k2, N, _p(sets), _p(w), _p(counts), cap, _p(rowptr), _p(cols), _p(vals), _stream())

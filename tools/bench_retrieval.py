@@ -40,7 +40,7 @@ sys.path.insert(0, os.path.join(REPO, "reid-gan_amd"))
 import torch
 import torch.nn.functional as F
 from rg_hip import ops
-from clustercontrast.evaluators import _dist_block
+from rg_hip.search import dist_block
 dev = torch.device("cuda", 0)
 
 
@@ -289,7 +289,7 @@ def evaluate_mode(spec, reps, noise):
     x = F.normalize(centres[ids] + noise * torch.randn(Q + G, D, generator=g, device=dev) / D ** 0.5, dim=1)
     ids = ids.int()
     qid, gid, qcam, gcam = ids[:Q].contiguous(), ids[Q:].contiguous(), cams[:Q].contiguous(), cams[Q:].contiguous()
-    dist = _dist_block(x[:Q].contiguous(), x[Q:].contiguous(), 1.0, True)
+    dist = dist_block(x[:Q].contiguous(), x[Q:].contiguous(), 1.0, True)
     out = dict(npos=torch.empty(Q, dtype=torch.int32, device=dev), ap=torch.empty(Q, dtype=torch.float64, device=dev),
                first=torch.empty(Q, dtype=torch.int32, device=dev), hits=torch.empty((Q, topk), dtype=torch.int32, device=dev),
                counts=torch.empty(topk + 2, dtype=torch.int32, device=dev), sums=torch.empty(topk + 1, dtype=torch.float64, device=dev))
@@ -401,7 +401,7 @@ def timeit(fn, reps=3):
 t_knn = timeit(knn)
 q = F.normalize(torch.randn(3368, 2048, generator=g, device=dev), dim=1)
 gal = F.normalize(torch.randn(15913, 2048, generator=g, device=dev), dim=1)
-t_dist = timeit(lambda: _dist_block(q, gal, 1.0, True))
+t_dist = timeit(lambda: dist_block(q, gal, 1.0, True))
 print(json.dumps({"knn_12936x2048_k15_ms": round(t_knn * 1e3, 2), "knn_gemm_tflops": round(2 * 12936 ** 2 * 2048 / t_knn / 1e12, 1),
                   "pairwise_3368x15913x2048_ms": round(t_dist * 1e3, 2),
                   "pairwise_tflops": round(2 * 3368 * 15913 * 2048 / t_dist / 1e12, 1)}))
