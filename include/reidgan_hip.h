@@ -648,6 +648,33 @@ int rg_mp_head_bwd(const float* dy_g, const float* dy_p1, const float* dy_p2, co
                    float* dgamma_g, float* dgamma_p1, float* dgamma_p2, float* dbeta_g, float* dbeta_p1, float* dbeta_p2, int B,
                    int D, int train, int fusion, rg_stream_t stream);
 
+/* ---- fused verification head of FD-GAN stage I, FD/reid/models/embedding.py:7-39 (use_batch_norm, use_classifier) under
+ * nn.CrossEntropyLoss() and FD/reid/evaluation_metrics/classification.py -------------------------------------------------------
+ * d = (x1 - x2)^2 [B][D], z = BatchNorm1d(d) (train: biased batch statistics, running statistics updated with the unbiased
+ * variance; eval: running statistics), logits = z W^T + bias with W [C][D], 1 <= C <= 16 (bias may be NULL).  With labels
+ * (int64 [B], may be NULL): loss_rows[b] = logsumexp(logits_b) - logits_b[label_b], out2 = {mean_b loss_rows, correct / B} where
+ * correct counts the rows whose argmax is the label (a tie goes to the LOWEST class index), dlogits = (softmax - onehot) / B.
+ * A label outside [0, C) gives its row loss 0 and a zero dlogits row, as rg_softmax_ce_fwd; the mean still divides by B.
+ *   forward   logits [B][C]; saved for the backward: xhat [B][D] (the normalised d), mean / invstd [D] (the batch statistics, or
+ *             the running mean and rsqrt(running_var + eps) in eval mode); with labels also loss_rows [B], out2 [2], dlogits
+ *             [B][C] (all three required then, ignored otherwise).  Train: 2 launches and rg_verif_head_workspace bytes of
+ *             workspace (B >= 2); eval: 1 launch, no workspace (workspace may be NULL), one more launch with labels.
+ *   backward  the logit gradient is grad_loss[0] * dlogits + dlogits_up: grad_loss is a 1-element device tensor (NULL = 1),
+ *             dlogits the forward's (NULL = the loss takes no part, grad_loss must be NULL too), dlogits_up [B][C] an upstream
+ *             gradient of the logits themselves (may be NULL); one of the two is given.  x1 and x2 are read again; no [B][D]
+ *             tensor besides xhat is kept.  dx1 / dx2 [B][D], dW [C][D], dbias [C], dgamma / dbeta [D]: each may be NULL.
+ *             1 launch.
+ * Deterministic (fixed summation order, no atomics). */
+int64_t rg_verif_head_workspace(int B, int D, int C);
+int rg_verif_head_fwd(const float* x1, const float* x2, const float* gamma, const float* beta, float* running_mean,
+                      float* running_var, const float* W, const float* bias, const int64_t* labels, float* logits, float* xhat,
+                      float* mean, float* invstd, float* loss_rows, float* out2, float* dlogits, int B, int D, int C, int train,
+                      float eps, float momentum, void* workspace, size_t workspace_bytes, rg_stream_t stream);
+int rg_verif_head_bwd(const float* grad_loss, const float* dlogits, const float* dlogits_up, const float* x1, const float* x2,
+                      const float* xhat, const float* invstd, const float* gamma, const float* beta, const float* W, float* dx1,
+                      float* dx2, float* dW, float* dbias, float* dgamma, float* dbeta, int B, int D, int C, int train,
+                      rg_stream_t stream);
+
 /* ---- losses (scalar outputs live in device memory; grad_out is a 1-element device tensor or NULL) */
 size_t rg_loss_workspace(void);
 /* GANLoss: sigmoid + BCE vs constant target, FD/fdgan/losses.py:29-32 */

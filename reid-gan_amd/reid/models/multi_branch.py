@@ -70,6 +70,63 @@ class SiameseNet(RGModule):
             return [self(x1, x2)[-1] for x2 in x2_list]
         return list(run(_SharedProgram(self), x1, *x2_list))
 
+    # ---- stage I: both branches, the verification head, its cross entropy and precision as ONE program --------------------------
+    def forward_loss(self, x1, x2, targets):
+        """-> (f1, f2, logits, loss, prec): `self(x1, x2)` plus nn.CrossEntropyLoss()(logits, targets) and the top-1 precision of
+        FD/reid/evaluation_metrics/classification.py as 0-d device tensors (FD/reid/trainers.py:69-73), the head on
+        csrc/verif_head.hip.  The trunk runs as in `tf`: x1 then x2 while its BatchNorm layers are in train mode (their running
+        statistics move twice, as in the reference), one batched pass when every one of them is in eval mode."""
+        if self.embed_model is None or not getattr(self.embed_model, "has_fused_loss", False):
+            raise RuntimeError("SiameseNet.forward_loss needs an EltwiseSubEmbed with BatchNorm and classifier")
+        prog = self.__dict__.get("_loss_program")
+        if prog is None or prog.net is not self:      # one object per net (a copied net brings the original's along): `run` keeps
+                                                      # the parameter list on it
+            prog = self.__dict__["_loss_program"] = _LossProgram(self)
+        return run(prog, x1, x2, targets)
+
+
+class _LossProgram(object):
+    """tape program of SiameseNet.forward_loss over the net's own submodules (not an nn.Module: it owns no parameters)."""
+
+    def __init__(self, net):
+        self.net = net
+
+    def parameters(self):
+        return self.net.parameters()
+
+    @property
+    def _rg_frozen(self):
+        return getattr(self.net, "_rg_frozen", False)
+
+    def tf(self, tape, x1, x2, targets):
+        net, b = self.net, x1.shape[0]
+        batched = bn_all_eval(net.base_model) and x1.shape[1:] == x2.shape[1:]
+        if batched:
+            f = net.base_model.tf(tape, torch.cat([x1, x2], 0))
+            f1, f2 = f[:b], f[b:]
+        else:
+            f1 = net.base_model.tf(tape, x1)
+            f2 = net.base_model.tf(tape, x2)
+        tape.push((batched, b))
+        logits, loss, prec = net.embed_model.tf_loss(tape, f1, f2, targets)
+        return f1, f2, logits, loss, prec
+
+    def tb(self, tape, d1, d2, dlogits, dloss, dprec=None, need_dx=True):
+        net = self.net
+        e1, e2 = net.embed_model.tb_loss(tape, dlogits, dloss)
+        batched, b = tape.pop()
+        if e1 is not None:
+            d1 = e1 if d1 is None else ops.add(d1, e1)
+            d2 = e2 if d2 is None else ops.add(d2, e2)
+        if d1 is None or d2 is None:
+            raise RuntimeError("SiameseNet.forward_loss: nothing that was differentiated reaches both branches")
+        if batched:
+            dx = net.base_model.tb(tape, torch.cat([d1, d2], 0), need_dx=need_dx)
+            return (dx[:b], dx[b:], None) if need_dx else (None, None, None)
+        dx2 = net.base_model.tb(tape, d2, need_dx=need_dx)
+        dx1 = net.base_model.tb(tape, d1, need_dx=need_dx)
+        return dx1, dx2, None
+
 
 class _SharedProgram(object):
     """tape program over SiameseNet's own submodules (not an nn.Module: it owns no parameters)."""

@@ -14,7 +14,7 @@ unit(s) it calls.
     eltwise    csrc/eltwise.hip, bgemm.hip, resize.hip: act, axpby, fills, dropout, l2norm, channel copies, softmax, bgemm, bicubic
     gan        csrc/gan_extra.hip: avgpool2d, reflection padding, spectral normalisation
     pool       csrc/pool.hip, part_head.hip: maxpool, global average, GeM, part pooling, the multi-part head
-    loss       csrc/loss.hip
+    loss       csrc/loss.hip, verif_head.hip: the losses, the fused verification head
     retrieval  csrc/cm.hip, retrieval.hip, rerank.hip, rank_eval.hip: cluster memory, kNN helpers, sort segments and label
                compaction (torch), re-ranking, CMC / mAP
     dbscan     csrc/dbscan.hip
@@ -55,7 +55,8 @@ from .pool import (maxpool2d_fwd, maxpool2d_bwd, global_avgpool_fwd, global_avgp
                    part_pool_fwd, part_pool_bwd, mp_head_fwd, mp_head_bwd)
 from .loss import (sigmoid_bce_fwd, sigmoid_bce_bwd, mse_const_fwd, mse_const_bwd, affine_relu_mean_fwd, affine_relu_mean_bwd,
                    grad_penalty_rows, l1_fwd, l1_bwd, l1_rows_fwd, l1_rows_bwd, mse_const_rows_fwd, mse_const_rows_bwd,
-                   softmax_ce_fwd, softmax_ce_bwd, softmax_ce_ext_fwd, softmax_ce_ext_bwd, weighted_sum_fwd, weighted_sum_bwd)
+                   softmax_ce_fwd, softmax_ce_bwd, softmax_ce_ext_fwd, softmax_ce_ext_bwd, weighted_sum_fwd, weighted_sum_bwd,
+                   verif_head_fwd, verif_head_bwd)
 from .retrieval import (cm_update, normalize_listed_rows, topk_rows, row_sqsum, add_outer_terms, segment_mean, sorted_segments,
                         compact_labels, rerank_expand, rerank_weights, rerank_query_expand, rerank_columns, rerank_jaccard,
                         rerank_orig_dist, rerank_from_rank, rank_eval)
@@ -81,7 +82,7 @@ from ._base import _DEV, _bind_device, _dense, _chk_rr, _nchw, _same_size, _eps3
 from .streams import _HANDED, _PROBE_US, _share_a_queue, _INLINE_SIDE, _SideSession, _SIDE_MIN_US, _GRAPH_SIDE_MIN_US
 from .norm import _BN_FUSED
 from .eltwise import _CONST_FILL, _CLOCK
-from .loss import _loss_ws
+from .loss import _loss_ws, _verif_vec
 from .dbscan import _chk_dbscan_matrix, _chk_dbscan_lists, _nbr_ptr
 from .infomap import _chk_infomap_table, _chk_infomap_graph, _infomap_level, _infomap_aggregate
 from .kmeans import _chk_kmeans_shape, _row_sqsum

@@ -1,9 +1,9 @@
-"""Loss kernels (csrc/loss.hip): forward values and their gradients."""
+"""Loss kernels (csrc/loss.hip): forward values and their gradients; the fused verification head (csrc/verif_head.hip)."""
 from __future__ import absolute_import
 
 import torch
 
-from ._base import _chk, _p, _same_size, _stream, lib, workspace
+from ._base import _chk, _dense, _p, _same_size, _stream, _ws_query, lib, workspace
 
 
 # ------------------------------------------------------------------------------------------------
@@ -176,6 +176,90 @@ def softmax_ce_ext_bwd(la, lb, labels, lse, grad_rows, group, mask, scale=1.0, g
     lib.rg_softmax_ce_ext_bwd(_p(la), _p(lb), _p(labels), _p(lse), _p(grad_rows), grad_scale, _p(dla), _p(dlb), n, m, t, group,
                               mask, scale, _stream())
     return dla, dlb
+
+
+def _verif_vec(t, name, n):
+    t = _dense(t, name)
+    if t is not None and t.numel() != n:
+        raise ValueError("rg_hip: verif_head %s must hold %d elements, got shape %s" % (name, n, tuple(t.shape)))
+    return t
+
+
+def verif_head_fwd(x1, x2, gamma, beta, running_mean, running_var, weight, bias, labels, train, eps, momentum):
+    """The verification head of FD-GAN stage I (csrc/verif_head.hip): logits = Linear(BatchNorm1d((x1 - x2)^2)) and, with
+    `labels` (int64 [B]), its mean cross entropy and top-1 precision.  x1, x2 [B, D]; weight [C, D], C <= 16; bias [C] or None.
+    Train mode updates running_mean / running_var in place.
+    -> logits [B, C], xhat [B, D], mean [D], invstd [D], loss_rows [B], out2 [2] = (loss, correct / B), dlogits [B, C] =
+    (softmax - onehot) / B; the last three are None without labels"""
+    x1, x2 = _dense(x1, "x1"), _dense(x2, "x2")
+    if x1.dim() != 2 or x1.shape != x2.shape:
+        raise ValueError("rg_hip: verif_head_fwd inputs must share one [B, D] shape, got %s and %s" % (tuple(x1.shape), tuple(x2.shape)))
+    B, D = x1.shape
+    weight = _dense(weight, "weight")
+    if weight.dim() != 2 or weight.shape[1] != D:
+        raise ValueError("rg_hip: verif_head_fwd weight must be [C, %d], got %s" % (D, tuple(weight.shape)))
+    C = weight.shape[0]
+    gamma, beta = _verif_vec(gamma, "gamma", D), _verif_vec(beta, "beta", D)
+    bias = _verif_vec(bias, "bias", C)
+    for name, t in (("running_mean", running_mean), ("running_var", running_var)):     # updated in place: a copy would be lost
+        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != D:
+            raise ValueError("rg_hip: verif_head_fwd %s must be a contiguous float32 GPU tensor of %d elements" % (name, D))
+    if train and B < 2:
+        raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(x1.shape),))
+    labels = _chk(labels, "labels", torch.int64)
+    if labels is not None and labels.numel() != B:
+        raise ValueError("rg_hip: verif_head_fwd takes one label per row, got %d for %d rows" % (labels.numel(), B))
+    dev = x1.device
+    logits = torch.empty((B, C), dtype=torch.float32, device=dev)
+    xhat = torch.empty((B, D), dtype=torch.float32, device=dev)
+    mean = torch.empty(D, dtype=torch.float32, device=dev)
+    invstd = torch.empty(D, dtype=torch.float32, device=dev)
+    loss_rows = out2 = dlogits = None
+    if labels is not None:
+        loss_rows = torch.empty(B, dtype=torch.float32, device=dev)
+        out2 = torch.empty(2, dtype=torch.float32, device=dev)
+        dlogits = torch.empty((B, C), dtype=torch.float32, device=dev)
+    ws = workspace(_ws_query("rg_verif_head_workspace", B, D, C), dev) if train else None
+    lib.rg_verif_head_fwd(_p(x1), _p(x2), _p(gamma), _p(beta), _p(running_mean), _p(running_var), _p(weight), _p(bias), _p(labels),
+                          _p(logits), _p(xhat), _p(mean), _p(invstd), _p(loss_rows), _p(out2), _p(dlogits), B, D, C,
+                          1 if train else 0, float(eps), float(momentum), _p(ws), ws.numel() if ws is not None else 0, _stream())
+    return logits, xhat, mean, invstd, loss_rows, out2, dlogits
+
+
+def verif_head_bwd(grad_loss, dlogits, dlogits_up, x1, x2, xhat, invstd, gamma, beta, weight, train, need_dx=(True, True),
+                   need_dweight=True, need_dbias=True, need_dgamma=True, need_dbeta=True, out=(None, None, None, None)):
+    """The logit gradient is grad_loss (1-element device tensor, None = 1) * dlogits (the forward's, None = no loss) + dlogits_up
+    (an upstream gradient of the logits, or None).  out: destinations for (dweight, dbias, dgamma, dbeta), None = allocate.
+    -> dx1, dx2, dweight, dbias, dgamma, dbeta (None where not needed)"""
+    x1, x2, xhat = _dense(x1, "x1"), _dense(x2, "x2"), _dense(xhat, "xhat")
+    B, D = xhat.shape
+    weight = _dense(weight, "weight")
+    C = weight.shape[0]
+    if tuple(x1.shape) != (B, D) or tuple(x2.shape) != (B, D) or weight.shape[1] != D:
+        raise ValueError("rg_hip: verif_head_bwd shapes do not match xhat %s" % (tuple(xhat.shape),))
+    if dlogits is None and dlogits_up is None:
+        raise ValueError("rg_hip: verif_head_bwd needs dlogits or dlogits_up")
+    grad_loss = _dense(grad_loss, "grad_loss") if dlogits is not None else None
+    dlogits, dlogits_up = _dense(dlogits, "dlogits"), _dense(dlogits_up, "dlogits_up")
+    for name, t in (("dlogits", dlogits), ("dlogits_up", dlogits_up)):
+        if t is not None and t.numel() != B * C:
+            raise ValueError("rg_hip: verif_head_bwd %s must be [%d, %d], got %s" % (name, B, C, tuple(t.shape)))
+    gamma, beta, invstd = _verif_vec(gamma, "gamma", D), _verif_vec(beta, "beta", D), _verif_vec(invstd, "invstd", D)
+    dev = xhat.device
+
+    def dst(need, given, shape):
+        if not need:
+            return None
+        if given is not None and given.is_contiguous() and given.numel() == (shape[0] if len(shape) == 1 else shape[0] * shape[1]):
+            return given
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    dx1 = torch.empty((B, D), dtype=torch.float32, device=dev) if need_dx[0] else None
+    dx2 = torch.empty((B, D), dtype=torch.float32, device=dev) if need_dx[1] else None
+    dw, db = dst(need_dweight, out[0], (C, D)), dst(need_dbias, out[1], (C,))
+    dga, dbe = dst(need_dgamma, out[2], (D,)), dst(need_dbeta, out[3], (D,))
+    lib.rg_verif_head_bwd(_p(grad_loss), _p(dlogits), _p(dlogits_up), _p(x1), _p(x2), _p(xhat), _p(invstd), _p(gamma), _p(beta),
+                          _p(weight), _p(dx1), _p(dx2), _p(dw), _p(db), _p(dga), _p(dbe), B, D, C, 1 if train else 0, _stream())
+    return dx1, dx2, dw, db, dga, dbe
 
 
 def weighted_sum_fwd(x, w=None, scale=1.0):

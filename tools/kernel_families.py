@@ -45,6 +45,9 @@ FAMILY = {
     # part_head.hip
     "mp_head_col_fwd_kernel": "norm", "mp_head_row_fwd_kernel": "norm", "mp_head_eval_fwd_kernel": "norm",
     "mp_head_row_bwd_kernel": "norm", "mp_head_col_bwd_kernel": "norm",
+    # verif_head.hip
+    "verif_head_col_fwd_kernel": "norm", "verif_head_eval_fwd_kernel": "norm", "verif_head_row_kernel": "norm",
+    "verif_head_col_bwd_kernel": "norm",
     # optim.hip
     "adam_advance_kernel": "optim", "adam_dev_kernel": "optim", "adam_kernel": "optim", "sgd_kernel": "optim",
     "u64_add_kernel": "optim",
