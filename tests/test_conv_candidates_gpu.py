@@ -8,26 +8,22 @@ unwritten cannot inherit the previous candidate's value.
 
 Bound, per element: |out - ref| <= 2^-20 * (|a| (*) |b|) + 1e-30, where (|a| (*) |b|) is the same contraction on absolute values
 (plus the absolute epilogue operands), all in fp64 on the device with no project kernel involved.  One dropped or doubled term of
-a reduction exceeds it; the split-bf16 products with fp32 accumulation land near 2^-24 of it."""
+a reduction exceeds it; the split-bf16 products with fp32 accumulation land near 2^-24 of it.  The references, _Sweep and the
+NaN-buffer helpers live in tests/conv_sweep.py, shared with the ragged-geometry sweep (tests/test_conv_ragged_gpu.py)."""
 import math
 import os
 import time
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.conv_sweep import (ALL_KINDS, FAMILY_OF, SLOPE, TINY, TOL, _Sweep, _guard_ok, _nan_buffer, _out_hw, _ratio, _workspace,
+                              ref_dgrad, ref_fwd, ref_wgrad)
+
 pytestmark = pytest.mark.gpu
 
 CHOICES = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "conv_choices_mi355x.txt")
-ALL_KINDS = (1, 2, 4, 16, 32, 64, 128, 256)
-FAMILY_OF = {1: "fwd", 16: "fwd", 64: "fwd", 2: "dgrad", 32: "dgrad", 128: "dgrad", 4: "wgrad", 256: "wgrad"}
-LEVELS = {"fwd": (16, 64, 1), "dgrad": (32, 128, 2), "wgrad": (256, 4)}     # outer -> inner: path, plan, implementation
-TOL = 2.0 ** -20
-TINY = 1e-30
-SLOPE = float(np.float32(0.2))
-CHUNK_BYTES = 1 << 30           # fp64 unfolded columns per reference chunk
 
 
 def _lib():
@@ -64,60 +60,6 @@ def _calls(rows):
     return calls
 
 
-def _out_hw(H, W, KH, KW, SH, SW, PH, PW):
-    return (H + 2 * PH - KH) // SH + 1, (W + 2 * PW - KW) // SW + 1
-
-
-def _chunks(N, per_sample_bytes):
-    step = max(1, CHUNK_BYTES // max(1, per_sample_bytes))
-    for n0 in range(0, N, step):
-        yield n0, min(N, n0 + step)
-
-
-# ---- fp64 references on the device (torch unfold / fold / matmul only), each with its contraction on absolute values ----
-def ref_fwd(x, w, stride, pad):
-    N, C, H, W = x.shape
-    K, _, KH, KW = w.shape
-    P, Q = _out_hw(H, W, KH, KW, stride[0], stride[1], pad[0], pad[1])
-    wm = w.reshape(K, -1)
-    wa = wm.abs()
-    y = torch.empty((N, K, P * Q), dtype=torch.float64, device=x.device)
-    a = torch.empty_like(y)
-    for n0, n1 in _chunks(N, 2 * C * KH * KW * P * Q * 8):
-        cols = F.unfold(x[n0:n1], (KH, KW), padding=pad, stride=stride)
-        y[n0:n1] = torch.matmul(wm, cols)
-        a[n0:n1] = torch.matmul(wa, cols.abs_())
-    return y.view(N, K, P, Q), a.view(N, K, P, Q)
-
-
-def ref_dgrad(dy, w, hw, stride, pad):
-    N, K, P, Q = dy.shape
-    _, C, KH, KW = w.shape
-    wt = w.reshape(K, -1).t()
-    wa = wt.abs()
-    dx = torch.empty((N, C) + tuple(hw), dtype=torch.float64, device=dy.device)
-    a = torch.empty_like(dx)
-    for n0, n1 in _chunks(N, C * KH * KW * P * Q * 8):
-        d = dy[n0:n1].reshape(n1 - n0, K, P * Q)
-        dx[n0:n1] = F.fold(torch.matmul(wt, d), hw, (KH, KW), padding=pad, stride=stride)
-        a[n0:n1] = F.fold(torch.matmul(wa, d.abs()), hw, (KH, KW), padding=pad, stride=stride)
-    return dx, a
-
-
-def ref_wgrad(x, dy, ksize, stride, pad):
-    N, C, H, W = x.shape
-    K, P, Q = dy.shape[1], dy.shape[2], dy.shape[3]
-    KH, KW = ksize
-    g = torch.zeros((K, C * KH * KW), dtype=torch.float64, device=x.device)
-    a = torch.zeros_like(g)
-    for n0, n1 in _chunks(N, 2 * C * KH * KW * P * Q * 8):
-        cols = F.unfold(x[n0:n1], (KH, KW), padding=pad, stride=stride)
-        d = dy[n0:n1].reshape(n1 - n0, K, P * Q)
-        g += torch.matmul(d, cols.transpose(1, 2)).sum(0)
-        a += torch.matmul(d.abs(), cols.abs_().transpose(1, 2)).sum(0)
-    return g.view(K, C, KH, KW), a.view(K, C, KH, KW)
-
-
 @pytest.mark.parametrize("geom", [(2, 5, 7, 6, 4, 3, 3, 1, 1, 1, 1),        # 3x3 / stride 1 / pad 1
                                   (3, 4, 10, 9, 6, 4, 4, 2, 2, 1, 1),       # strided 4x4, odd width (an uncovered column)
                                   (2, 8, 5, 3, 7, 1, 1, 1, 1, 0, 0)])       # 1x1
@@ -146,90 +88,6 @@ def test_fp64_reference_matches_cpu_autograd(dev, geom):
             assert v.shape == r.shape, (name, part)
             err = (v - r).abs().max().item()
             assert err <= 1e-12 * r.abs().max().item(), "%s %s: %.3e" % (name, part, err)
-
-
-class _Sweep(object):
-    def __init__(self, lib):
-        self.lib = lib
-        self.buf = np.zeros(18 * 64, dtype=np.int32)
-        self.keys = {}                          # every key the library reported -> its candidate count
-        self.worst = {}                         # check name -> worst ratio
-        self.count = {"fwd": 0, "dgrad": 0, "wgrad": 0}
-        self.calls = {"fwd": 0, "dgrad": 0, "wgrad": 0}
-        self.bad = []
-
-    def log(self):
-        n = self.lib.rg_conv_pick_log(self.buf.ctypes.data, 64)
-        assert 0 <= n <= 64, n
-        recs = self.buf[:18 * n].reshape(n, 18)
-        out = {}
-        for r in recs:
-            key, ncand, idx = tuple(int(v) for v in r[:16]), int(r[16]), int(r[17])
-            assert key[0] not in out, "two choices of kind %d in one call" % key[0]
-            out[key[0]] = (key, ncand, idx)
-            assert self.keys.setdefault(key, ncand) == ncand, ("candidate count of a key changed", key)
-        return out
-
-    def sweep(self, fam, label, launch, check):
-        """runs every combination of the family's nested choices exactly once: a run with the inner levels at 0 reports how many
-        candidates each inner level has under the pinned outer ones"""
-        levels = LEVELS[fam]
-        results = []
-
-        def run(pins):
-            for kind, i in zip(levels, pins):
-                self.lib.rg_conv_set_pick(kind, i)
-            launch()
-            recs = self.log()
-            for kind, i in zip(levels, pins):
-                if kind in recs:
-                    assert recs[kind][2] == i, (label, pins, recs[kind])
-                else:
-                    assert i == 0, (label, pins, kind)
-            results.append((pins, check()))
-            return {k: v[1] for k, v in recs.items()}
-
-        def visit(prefix):
-            pins = prefix + [0] * (len(levels) - len(prefix))
-            nc = run(pins)
-            for j in range(len(prefix), len(levels)):
-                for i in range(1, nc.get(levels[j], 1)):
-                    visit(prefix + [0] * (j - len(prefix)) + [i])
-
-        visit([])
-        for kind in levels:
-            self.lib.rg_conv_set_pick(kind, 0)
-        names = list(results[0][1].keys())
-        ratios = torch.stack([torch.stack([r[n] for n in names]) for _, r in results]).cpu().numpy()
-        for ci, (pins, _) in enumerate(results):
-            for ni, n in enumerate(names):
-                v = float(ratios[ci, ni])
-                self.worst[n] = max(self.worst.get(n, 0.0), v)
-                if not v <= 1.0:
-                    self.bad.append("%s %s pins %s: %s ratio %.3g" % (label, fam, dict(zip(levels, pins)), n, v))
-        self.count[fam] += len(results)
-        self.calls[fam] += 1
-
-
-def _ratio(out, ref, tol):
-    q = (out.double() - ref).abs_().div_(tol)
-    return torch.nan_to_num(q, nan=math.inf, posinf=math.inf).amax()
-
-
-def _nan_buffer(numel, dev, guard=256):
-    """output storage with a NaN guard behind it (a store past the end shows up as a written guard)"""
-    buf = torch.empty(numel + guard, dtype=torch.float32, device=dev)
-    return buf, buf[:numel], buf[numel:]
-
-
-def _guard_ok(ratio, guard):
-    return torch.where(guard.isnan().all(), ratio, torch.full_like(ratio, math.inf))
-
-
-def _workspace(nbytes, dev):
-    if not nbytes:
-        return None
-    return torch.empty((int(nbytes) + 3) // 4, dtype=torch.float32, device=dev)
 
 
 def _sweep_fwd(sw, lib, dev, stream, geom, epis, gen):

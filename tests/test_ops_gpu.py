@@ -28,6 +28,7 @@ def _close(got, ref, tol=2e-5, name=""):
 
 
 # (N, C, H, W, K, KH, KW, stride, pad)   — every geometry of the reference networks at reduced batch/width
+# (per element, every candidate kernel and forced plan at ragged shapes: tests/test_conv_ragged_gpu.py)
 CONV_CASES = [
     (2, 3, 64, 32, 64, 7, 7, 2, 3),      # ResNet stem (Kg = 147, scalar weight path)
     (2, 64, 16, 8, 64, 1, 1, 1, 0),      # bottleneck 1x1
