@@ -675,6 +675,31 @@ int rg_verif_head_bwd(const float* grad_loss, const float* dlogits, const float*
                       float* dx2, float* dW, float* dbias, float* dgamma, float* dbeta, int B, int D, int C, int train,
                       rg_stream_t stream);
 
+/* ---- second stage of the cascade evaluation, FD/reid/evaluators.py:19-43 and :198-227 (csrc/cascade.hip) -----------------------
+ * rg_pair_score: the verification head above in eval mode on GATHERED pairs.  Pair (q, j) is probe row q against gallery row
+ * idx[q][j]:  d = (probe_q - g)^2,  z = gamma (d - running_mean) rsqrt(running_var + eps) + beta,  logits[c] = sum_ch z[ch]
+ * W[c][ch] + bias[c] (bias may be NULL),  score = softmax(logits)[0] = 1 / sum_c exp(l_c - l_0), computed with the maximum
+ * subtracted first (no overflow; exactly 1 for C == 1).  logits [Q][k][C] and score [Q][k] may each be NULL, not both.
+ * Limits: 1 <= C <= 16, 1 <= D <= 8192, 1 <= k <= G, 1 <= Q <= 65535, Q k C < 2^31.  The per-channel constants a = gamma
+ * rsqrt(running_var + eps) and t_c = W_c a are folded once per D-chunk and shared by the rows in flight, K_c = sum_ch beta W_c +
+ * bias_c once per workgroup (all read through the cache); running_mean is subtracted from d before the scaling.  No [Q k][D] or [Q][G] temporary and no workspace.  An index outside [0, G) is the
+ * caller's error: nothing is read for that pair and NaN is written.  One wave sums a pair in an order that depends on D alone:
+ * the same bits for any grid, stream or chunking of the queries.  No atomics.
+ * rg_pair_score_regime: which launch regime the shape takes (a value, not a status; -1 outside the limits): bit 0 16-byte
+ * loads (D a multiple of 4 and `aligned`, the 16-byte alignment of the arrays; else 4-byte loads), bit 1 k is split over several
+ * workgroups per query (Q below the CU count).
+ * rg_cascade_merge: the reference's "merge two-stage distances" in place on dist [Q][ld] (ld >= G).  The k indices of a row are
+ * distinct (a top-k); with S the set of columns idx[q][:], in float32 and in this order: nxt = min_{j not in S} dist[q][j] on
+ * the first-stage values, bar = max_j score[q][j], gap = max((bar + 1) - nxt, 0), dist[q][idx[q][j]] = score[q][j], dist[q][j]
+ * += gap for j not in S when gap > 0.  k == G: the overwrite alone.  Membership comes from idx (a bitmap of G bits in LDS,
+ * G <= 1 048 576), never from comparing distances.  A row that holds a NaN comes back unspecified; nothing is read or written
+ * out of bounds.  Bit-reproducible (no float atomics). */
+int64_t rg_pair_score_regime(int Q, int k, int D, int C, int aligned);
+int rg_pair_score(const float* probe, const float* gallery, const int* idx, const float* gamma, const float* beta,
+                  const float* running_mean, const float* running_var, const float* W, const float* bias, float* logits,
+                  float* score, int Q, int G, int k, int D, int C, float eps, rg_stream_t stream);
+int rg_cascade_merge(float* dist, int64_t ld, const int* idx, const float* score, int Q, int G, int k, rg_stream_t stream);
+
 /* ---- losses (scalar outputs live in device memory; grad_out is a 1-element device tensor or NULL) */
 size_t rg_loss_workspace(void);
 /* GANLoss: sigmoid + BCE vs constant target, FD/fdgan/losses.py:29-32 */

@@ -10,6 +10,10 @@ MI355X-first restatement of the second stage: the reference scores one query at 
 top-k of the distance matrix (`rg_topk_rows` on the negated distances, ties by lower index like a stable argsort), the
 top-k gallery rows of ALL queries are gathered into one [Q * k, 2048] operand and the embedding network (eltwise
 (x1 - x2)^2 -> BatchNorm1d -> Linear) runs once.  The merge of the two stages (:215-225) is unchanged arithmetic.
+
+Device-resident counterparts under names of their own, which need no reference tree: `extract_features_device`,
+`evaluate_all_device` and `DeviceCascadeEvaluator`.  Its second stage gathers the pairs inside `ops.pair_score`
+(csrc/cascade.hip: no [Q * k, 2048] operand is ever built) and merges in place on the device with `ops.cascade_merge`.
 """
 from __future__ import print_function, absolute_import
 
@@ -95,6 +99,175 @@ class CascadeEvaluator(object):
             distmat = self.second_stage(distmat, features, query, gallery, alpha, rerank_topk)
             print("Second stage evaluation:")
         return evaluate_all(distmat, query, gallery, dataset=dataset, top1=top1)                # noqa: F821
+
+
+# ------------------------------------------------------------------------------------------------
+# the device-resident cascade: needs no reference tree, nothing but ids, cameras and the scores crosses to the host
+# ------------------------------------------------------------------------------------------------
+PAIR_OPERAND_BYTES = 256 << 20      # composed path: the [q * k, D] operand of one chunk of queries stays at or below this
+
+
+def softmax_class0(x):
+    """F.softmax(x, dim=1)[:, 0]: the `embed_dist_fn` of baseline.py:106 and train.py:59 under a name, so that
+    DeviceCascadeEvaluator can recognise it and take the score from the pair-scoring kernel"""
+    return torch.nn.functional.softmax(x, dim=1)[:, 0]
+
+
+def extract_features_device(model, data_loader, print_freq=1):
+    """The reference's `extract_features` loop (:46-73) with the features kept on the device: (DeviceFeatures, labels).  Reads
+    the first three fields of a batch (imgs, fnames, pids), so the 4-tuples of this package's loaders and 5-tuples both work."""
+    import time
+    from collections import OrderedDict
+    from clustercontrast.evaluators import DeviceFeatures
+    from clustercontrast.utils.meters import AverageMeter
+    model.eval()
+    batch_time, data_time = AverageMeter(), AverageMeter()
+    blocks, index, labels = [], OrderedDict(), OrderedDict()
+    dev, base = search.device(), 0
+    end = time.time()
+    with torch.no_grad():
+        for i, batch in enumerate(data_loader):
+            imgs, fnames, pids = batch[0], batch[1], batch[2]
+            data_time.update(time.time() - end)
+            outputs = model(torch.as_tensor(imgs).to(dev, non_blocking=True)).data
+            blocks.append(outputs.reshape(outputs.shape[0], -1))
+            for j, (fname, pid) in enumerate(zip(fnames, pids)):
+                index[fname] = base + j
+                labels[fname] = pid
+            base += outputs.shape[0]
+            batch_time.update(time.time() - end)
+            end = time.time()
+            if (i + 1) % print_freq == 0:
+                print('Extract Features: [{}/{}]\t'
+                      'Time {:.3f} ({:.3f})\t'
+                      'Data {:.3f} ({:.3f})\t'
+                      .format(i + 1, len(data_loader),
+                              batch_time.val, batch_time.avg,
+                              data_time.val, data_time.avg))
+    return DeviceFeatures(torch.cat(blocks, 0), index), labels
+
+
+def evaluate_all_device(distmat, query=None, gallery=None,
+                        query_ids=None, gallery_ids=None,
+                        query_cams=None, gallery_cams=None,
+                        cmc_topk=(1, 5, 10), dataset=None, top1=True):
+    """The reference's `evaluate_all` (:101-181): same signature, printed lines and return values, from ONE `ops.rank_eval` pass
+    over the (device) matrix, which yields mAP, the `allshots` and the `market1501` CMC together.  top1=False returns the mAP; a
+    named dataset other than 'cuhk03' returns (market1501 top-1, mAP).
+    The `cuhk03` column (single_gallery_shot=True) goes through this build's `cmc`, which hands it to the reference's host
+    sampling: with dataset=None and with dataset='cuhk03' a run without the reference tree ends in that function's
+    NotImplementedError (after the 'Mean AP' line)."""
+    from clustercontrast.evaluation_metrics import ranking as R
+    if query is not None and gallery is not None:
+        query_ids = [pid for _, pid, _ in query]
+        gallery_ids = [pid for _, pid, _ in gallery]
+        query_cams = [cam for _, _, cam in query]
+        gallery_cams = [cam for _, _, cam in gallery]
+    else:
+        assert (query_ids is not None and gallery_ids is not None
+                and query_cams is not None and gallery_cams is not None)
+    res = R._score(distmat, query_ids, gallery_ids, query_cams, gallery_cams, 100, False)
+    mAP = float(res["ap_sum"] / res["num_valid"])
+    print('Mean AP: {:4.1%}'.format(mAP))
+    if not top1:
+        return mAP
+
+    def cuhk03():
+        return R.cmc(distmat, query_ids, gallery_ids, query_cams, gallery_cams, separate_camera_set=True,
+                     single_gallery_shot=True, first_match_break=False)
+    allshots = res["allshots"].cumsum() / res["num_valid"]
+    market = res["first_hist"].astype(np.float64).cumsum() / res["num_valid"]
+    if not dataset:
+        cmc_scores = {'allshots': allshots, 'cuhk03': cuhk03(), 'market1501': market}
+        print('CMC Scores{:>12}{:>12}{:>12}'
+              .format('allshots', 'cuhk03', 'market1501'))
+        for k in cmc_topk:
+            print('  top-{:<4}{:12.1%}{:12.1%}{:12.1%}'
+                  .format(k, cmc_scores['allshots'][k - 1],
+                          cmc_scores['cuhk03'][k - 1],
+                          cmc_scores['market1501'][k - 1]))
+        return cmc_scores['allshots'][0]
+    name = 'cuhk03' if dataset == 'cuhk03' else 'market1501'
+    scores = cuhk03() if name == 'cuhk03' else market
+    print('CMC Scores{:>12}'.format(name))
+    for k in cmc_topk:
+        print('  top-{:<4}{:12.1%}'
+              .format(k, scores[k - 1]))
+    return scores[0], mAP
+
+
+class DeviceCascadeEvaluator(object):
+    """`CascadeEvaluator` with features, distances, ranking, pair scores and the merged matrix kept on the device; works with no
+    reference tree.  The second stage is a device top-k, `ops.pair_score` (the embedding network on pairs gathered inside the
+    kernel: no [Q * k, D] operand) and `ops.cascade_merge` (in place)."""
+
+    def __init__(self, base_model, embed_model, embed_dist_fn=softmax_class0):
+        super(DeviceCascadeEvaluator, self).__init__()
+        self.base_model = base_model
+        self.embed_model = embed_model
+        self.embed_dist_fn = embed_dist_fn
+        self.last_path = None           # 'score' / 'logits' (the fused kernel) or 'composed', and the chunks the latter took
+        self.last_chunks = 0
+        self.last_distmat = None        # the matrix the last `evaluate` scored (device), for callers that go on with it
+
+    def fusable(self, D):
+        from reid.models.embedding import EltwiseSubEmbed
+        m = self.embed_model
+        return isinstance(m, EltwiseSubEmbed) and m.has_fused_loss and D <= ops.PAIR_SCORE_MAX_D
+
+    def pair_scores(self, probe, gallery, top, pair_bytes=PAIR_OPERAND_BYTES):
+        """[Q, k] second-stage distances of every query against the gallery rows `top` int32 [Q, k] lists"""
+        (Q, D), k, fn = probe.shape, top.shape[1], self.embed_dist_fn
+        m = self.embed_model
+        m.eval()
+        if self.fusable(D):
+            bn, fc = m.bn, m.classifier
+            fused = fn is softmax_class0
+            self.last_path, self.last_chunks = ('score' if fused else 'logits'), 1
+            logits, score = ops.pair_score(probe, gallery, top, bn.weight.detach(), bn.bias.detach(), bn.running_mean,
+                                           bn.running_var, fc.weight.detach(), None if fc.bias is None else fc.bias.detach(),
+                                           bn.eps, want_logits=not fused, want_score=fused)
+            if fused:
+                return score
+            emb = logits.view(Q * k, -1)
+            emb = fn(emb) if fn is not None else emb
+            return emb.detach().float().reshape(Q, k).contiguous()
+        rows = max(1, int(pair_bytes) // (k * D * 4))
+        out = torch.empty((Q, k), dtype=torch.float32, device=probe.device)
+        self.last_path, self.last_chunks = 'composed', 0
+        with torch.no_grad():
+            for q0 in range(0, Q, rows):
+                q1 = min(Q, q0 + rows)
+                x1 = probe[q0:q1].view(q1 - q0, 1, D).expand(q1 - q0, k, D).reshape((q1 - q0) * k, D).contiguous()
+                x2 = gallery.index_select(0, top[q0:q1].reshape(-1).long())
+                emb = m(x1, x2).view((q1 - q0) * k, -1)
+                emb = fn(emb.data) if fn is not None else emb
+                out[q0:q1] = emb.detach().float().reshape(q1 - q0, k)
+                self.last_chunks += 1
+        return out
+
+    def second_stage_device(self, distmat, probe, gallery, rerank_topk=75, pair_bytes=PAIR_OPERAND_BYTES):
+        """first-stage distances [Q, G] on the device -> the merged two-stage distances, written over `distmat` and returned
+        (:202-225).  probe [Q, D], gallery [G, D]: contiguous fp32 device tensors.  pair_bytes bounds the [q * k, D] operand
+        of the composed path (an embed model the kernel does not cover)."""
+        Q, G = distmat.shape
+        k = min(int(rerank_topk), G)
+        top = search.blocked_topk(Q, k, lambda r0, r1: ops.scale(distmat[r0:r1], -1.0))
+        score = self.pair_scores(probe, gallery, top, pair_bytes)
+        return ops.cascade_merge(distmat, top, score)
+
+    def evaluate(self, data_loader, query, gallery, alpha=0, cache_file=None, rerank_topk=75, second_stage=True, dataset=None,
+                 top1=True):
+        features, _ = extract_features_device(self.base_model, data_loader)
+        probe, gal = features.rows(query), features.rows(gallery)
+        distmat = search.dist_block(probe, gal, 1.0, True)
+        print("First stage evaluation:")
+        if second_stage:
+            evaluate_all_device(distmat, query=query, gallery=gallery, dataset=dataset, top1=top1)
+            distmat = self.second_stage_device(distmat, probe, gal, rerank_topk)
+            print("Second stage evaluation:")
+        self.last_distmat = distmat
+        return evaluate_all_device(distmat, query, gallery, dataset=dataset, top1=top1)
 
 
 # `extract_features`, `evaluate_all`, `Evaluator` are the reference's own host code (rg_hip/overlay.py); they score through this

@@ -1,5 +1,5 @@
-"""Cluster memory, kNN and row helpers of the pseudo-labelling code, k-reciprocal re-ranking, CMC / mAP scoring:
-csrc/cm.hip, csrc/retrieval.hip, csrc/rerank.hip, csrc/rank_eval.hip."""
+"""Cluster memory, kNN and row helpers of the pseudo-labelling code, k-reciprocal re-ranking, CMC / mAP scoring, the second stage
+of the cascade evaluation: csrc/cm.hip, csrc/retrieval.hip, csrc/rerank.hip, csrc/rank_eval.hip, csrc/cascade.hip."""
 from __future__ import absolute_import
 
 import torch
@@ -262,3 +262,78 @@ def rank_eval(dist, query_ids, gallery_ids, query_cams, gallery_cams, topk=100, 
     if debug:
         res.update(npos=npos, ap=ap, first=first, hits=hits)
     return res
+
+
+# ------------------------------------------------------------------------------------------------
+# second stage of the cascade evaluation (csrc/cascade.hip): the verification head on gathered pairs, the merge of the two stages
+# ------------------------------------------------------------------------------------------------
+PAIR_SCORE_MAX_C, PAIR_SCORE_MAX_D, PAIR_SCORE_MAX_Q, CASCADE_MERGE_MAX_G = 16, 8192, 32768, 1 << 20
+PAIR_VEC4, PAIR_SPLIT_K = 1, 2        # bits of pair_score_regime
+
+
+def pair_score_regime(Q, k, D, C, aligned=True):
+    """the launch regime `pair_score` takes at this shape, bits PAIR_VEC4 (16-byte loads, else 4-byte: D no multiple of 4) and
+    PAIR_SPLIT_K (k split over several workgroups per query: Q below the CU count).  `aligned` is always true for tensors that went through the wrapper."""
+    return int(lib.rg_pair_score_regime(int(Q), int(k), int(D), int(C), int(bool(aligned))))
+
+
+def _pair_vec(t, name, n):
+    t = _chk_rr(t, name, torch.float32, 1)
+    if t.numel() != n:
+        raise ValueError("rg_hip: pair_score %s must have %d elements, got %d" % (name, n, t.numel()))
+    return t.clone() if t.data_ptr() & 15 else t
+
+
+def pair_score(probe, gallery, idx, gamma, beta, running_mean, running_var, weight, bias, eps, want_logits=False, want_score=True,
+               chunk=PAIR_SCORE_MAX_Q):
+    """The eval-mode verification head (Linear(BatchNorm1d((x1 - x2)^2)), running statistics) of probe row q against the gallery
+    rows idx[q, :], gathered inside the kernel: probe [Q, D], gallery [G, D], idx int32 [Q, k] with entries in [0, G), weight
+    [C, D], bias [C] or None.  -> (logits [Q, k, C] or None, score [Q, k] or None), score = softmax(logits)[..., 0].
+    chunk = queries per launch (at most 32 768); the bits do not depend on it."""
+    probe, gallery = _chk_rr(probe, "probe", torch.float32, 2), _chk_rr(gallery, "gallery", torch.float32, 2)
+    idx, weight = _chk_rr(idx, "idx", torch.int32, 2), _chk_rr(weight, "weight", torch.float32, 2)
+    (Q, D), G, (C, k), chunk = probe.shape, gallery.shape[0], (weight.shape[0], idx.shape[1]), int(chunk)
+    if gallery.shape[1] != D or weight.shape[1] != D or idx.shape[0] != Q:
+        raise ValueError("rg_hip: pair_score: probe %s, gallery %s, idx %s, weight %s disagree"
+                         % (tuple(probe.shape), tuple(gallery.shape), tuple(idx.shape), tuple(weight.shape)))
+    if not (1 <= C <= PAIR_SCORE_MAX_C and 1 <= D <= PAIR_SCORE_MAX_D and 1 <= k <= G and Q >= 1):
+        raise ValueError("rg_hip: pair_score needs 1 <= C <= %d, 1 <= D <= %d, 1 <= k <= G and Q >= 1, got C=%d D=%d k=%d G=%d Q=%d"
+                         % (PAIR_SCORE_MAX_C, PAIR_SCORE_MAX_D, C, D, k, G, Q))
+    if not (want_logits or want_score):
+        raise ValueError("rg_hip: pair_score computes logits, score or both: one of want_logits and want_score")
+    if not 1 <= chunk <= PAIR_SCORE_MAX_Q or chunk * k * C >= 2 ** 31:
+        raise ValueError("rg_hip: pair_score: chunk must be 1 .. %d with chunk * k * C < 2^31, got %d" % (PAIR_SCORE_MAX_Q, chunk))
+    gamma, beta = _pair_vec(gamma, "gamma", D), _pair_vec(beta, "beta", D)
+    running_mean, running_var = _pair_vec(running_mean, "running_mean", D), _pair_vec(running_var, "running_var", D)
+    bias = None if bias is None else _pair_vec(bias, "bias", C)
+    if (probe.data_ptr() | gallery.data_ptr() | weight.data_ptr()) & 15:           # the rows are read as 16-byte vectors
+        probe, gallery, weight = (t.clone() if t.data_ptr() & 15 else t for t in (probe, gallery, weight))
+    dev = probe.device
+    logits = torch.empty((Q, k, C), dtype=torch.float32, device=dev) if want_logits else None
+    score = torch.empty((Q, k), dtype=torch.float32, device=dev) if want_score else None
+    for q0 in range(0, Q, chunk):
+        q1 = min(Q, q0 + chunk)
+        lib.rg_pair_score(_p(probe[q0:q1]), _p(gallery), _p(idx[q0:q1]), _p(gamma), _p(beta), _p(running_mean), _p(running_var),
+                          _p(weight), _p(bias), _p(None if logits is None else logits[q0:q1]),
+                          _p(None if score is None else score[q0:q1]), q1 - q0, G, k, D, C, float(eps), _stream())
+    return logits, score
+
+
+def cascade_merge(dist, idx, score):
+    """In place on dist [Q, G] (rows may be strided, columns not): the k columns idx[q, :] (int32, distinct per row) take
+    score[q, :], every other column moves up by gap = max((max_j score[q, j] + 1) - min of the other columns, 0), so that the
+    re-scored entries rank first (FD/reid/evaluators.py:218-226).  k == G: the overwrite alone.  Returns dist."""
+    for t, name, dt in ((dist, "dist", torch.float32), (idx, "idx", torch.int32), (score, "score", torch.float32)):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or t.dim() != 2:
+            raise ValueError("rg_hip: cascade_merge: %s must be a 2-D %s GPU tensor" % (name, dt))
+    idx, score = _chk_rr(idx, "idx", torch.int32, 2), _chk_rr(score, "score", torch.float32, 2)
+    _chk_rr(dist[0], "dist rows", torch.float32, 1)
+    (Q, G), k = dist.shape, idx.shape[1]
+    ld = dist.stride(0) if Q > 1 else max(G, dist.stride(0))
+    if tuple(idx.shape) != (Q, k) or tuple(score.shape) != (Q, k) or not 1 <= k <= G or ld < G:
+        raise ValueError("rg_hip: cascade_merge: dist %s (row stride %d), idx %s, score %s disagree (1 <= k <= G)"
+                         % (tuple(dist.shape), ld, tuple(idx.shape), tuple(score.shape)))
+    if G > CASCADE_MERGE_MAX_G:
+        raise ValueError("rg_hip: cascade_merge: at most %d gallery columns, got %d" % (CASCADE_MERGE_MAX_G, G))
+    lib.rg_cascade_merge(_p(dist), ld, _p(idx), _p(score), Q, G, k, _stream())
+    return dist
