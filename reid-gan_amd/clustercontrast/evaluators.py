@@ -7,13 +7,16 @@ only when its tree sits behind this one on sys.path: they are inherited at the b
 here, and import `cmc` / `mean_ap` from this build's `.evaluation_metrics` (scored on the device) and `re_ranking` from this
 build's `.utils.rerank`.  Their device-resident counterparts live here under names of their own — `extract_features_device`,
 `evaluate_all_device`, `DeviceEvaluator` — and need no reference tree: features, distance matrices and the re-ranked matrix stay
-on the device and one `ops.rank_eval` call scores mAP and the `market1501` CMC.
+on the device and one `ops.rank_eval` call scores mAP and the `market1501` CMC.  The collection loop behind
+`extract_features_device` and `DeviceFeatures` live in rg_hip/hostloop.py; `score_mean_ap`, the opening of `evaluate_all_device`,
+is defined here and serves reid/evaluators.py too.
 """
 from __future__ import print_function, absolute_import
 
 import torch
 
-from rg_hip import search
+from rg_hip import hostloop, search
+from rg_hip.hostloop import DeviceFeatures  # noqa: F401
 
 
 def _to_torch(x):
@@ -44,54 +47,9 @@ def pairwise_distance(features, query=None, gallery=None, return_device=False):
     return dist_m.cpu(), x.numpy(), y.numpy()
 
 
-class DeviceFeatures(object):
-    """What `extract_features_device` returns: all features as one [N, D] device tensor plus fname -> row.  `features[fname]`
-    is a row view, so the object also serves where the reference's OrderedDict of features is read."""
-
-    def __init__(self, matrix, index):
-        self.matrix, self.index = matrix, index
-
-    def __getitem__(self, fname):
-        return self.matrix[self.index[fname]]
-
-    def __len__(self):
-        return len(self.index)
-
-    def rows(self, entries):
-        """[len(entries), D] device block of the (fname, pid, cam) triples, one gather"""
-        idx = torch.as_tensor([self.index[f] for f, _, _ in entries], dtype=torch.int64).to(self.matrix.device)
-        return self.matrix.index_select(0, idx).view(len(entries), -1).float().contiguous()
-
-
 def extract_features_device(model, data_loader, print_freq=50):
     """The reference's `extract_features` loop (:30-68) with the features kept on the device: (DeviceFeatures, labels)."""
-    import time
-    from collections import OrderedDict
-    from .utils.meters import AverageMeter
-    model.eval()
-    batch_time, data_time = AverageMeter(), AverageMeter()
-    blocks, index, labels = [], OrderedDict(), OrderedDict()
-    dev = search.device()
-    end = time.time()
-    with torch.no_grad():
-        for i, (imgs, fnames, pids, _, _) in enumerate(data_loader):
-            data_time.update(time.time() - end)
-            outputs = model(_to_torch(imgs).to(dev, non_blocking=True)).data
-            base = sum(b.shape[0] for b in blocks)
-            blocks.append(outputs.reshape(outputs.shape[0], -1))
-            for k, (fname, pid) in enumerate(zip(fnames, pids)):
-                index[fname] = base + k
-                labels[fname] = pid
-            batch_time.update(time.time() - end)
-            end = time.time()
-            if (i + 1) % print_freq == 0:
-                print('Extract Features: [{}/{}]\t'
-                      'Time {:.3f} ({:.3f})\t'
-                      'Data {:.3f} ({:.3f})\t'
-                      .format(i + 1, len(data_loader),
-                              batch_time.val, batch_time.avg,
-                              data_time.val, data_time.avg))
-    return DeviceFeatures(torch.cat(blocks, 0), index), labels
+    return hostloop.collect_features(model, data_loader, print_freq)
 
 
 def pairwise_distance_device(features, query, gallery):
@@ -99,14 +57,10 @@ def pairwise_distance_device(features, query, gallery):
     return search.dist_block(features.rows(query), features.rows(gallery), 1.0, True)
 
 
-def evaluate_all_device(distmat, query=None, gallery=None,
-                        query_ids=None, gallery_ids=None,
-                        query_cams=None, gallery_cams=None,
-                        cmc_topk=(1, 5, 10), cmc_flag=False):
-    """The reference's `evaluate_all` (:91-122, without its two unused feature arguments) from one `ops.rank_eval` call: mAP and
-    the `market1501` CMC (first match, cameras not separated) come out of the same pass over the matrix.  Same printed lines
-    and return values."""
-    import numpy as np
+def score_mean_ap(distmat, query=None, gallery=None, query_ids=None, gallery_ids=None, query_cams=None, gallery_cams=None):
+    """The opening of both `evaluate_all_device`: ids and cameras from the (fname, pid, cam) triples of `query` / `gallery` or
+    from the four lists, one `ops.rank_eval` pass over the matrix, the 'Mean AP' line.  Returns the pass's results, the mAP and
+    the four lists."""
     from .evaluation_metrics import ranking as R
     if query is not None and gallery is not None:
         query_ids = [pid for _, pid, _ in query]
@@ -119,6 +73,18 @@ def evaluate_all_device(distmat, query=None, gallery=None,
     res = R._score(distmat, query_ids, gallery_ids, query_cams, gallery_cams, 100, False)
     mAP = float(res["ap_sum"] / res["num_valid"])
     print('Mean AP: {:4.1%}'.format(mAP))
+    return res, mAP, (query_ids, gallery_ids, query_cams, gallery_cams)
+
+
+def evaluate_all_device(distmat, query=None, gallery=None,
+                        query_ids=None, gallery_ids=None,
+                        query_cams=None, gallery_cams=None,
+                        cmc_topk=(1, 5, 10), cmc_flag=False):
+    """The reference's `evaluate_all` (:91-122, without its two unused feature arguments) from one `ops.rank_eval` call: mAP and
+    the `market1501` CMC (first match, cameras not separated) come out of the same pass over the matrix.  Same printed lines
+    and return values."""
+    import numpy as np
+    res, mAP, _ = score_mean_ap(distmat, query, gallery, query_ids, gallery_ids, query_cams, gallery_cams)
 
     if (not cmc_flag):
         return mAP

@@ -11,6 +11,10 @@ Same constructors, method names and arguments.  Differences that are scheduling 
     torch.distributed is initialised — the reference used single-process DataParallel;
   * wandb / tensorboard writers are optional (not installed on the target machines).
 The encoder's train-mode tuple output is accepted everywhere.
+
+The epoch loop (meters, deferred readback, print line, wandb), the update tail of a single-optimizer step (`zero_grad`, backward,
+reduce, `step`) and the batch's host->device copy are rg_hip/hostloop.py's, shared with reid/trainers.py; every loop here is
+`_EncoderTrainer._epoch` over a step.  `joint_step` and `GANTrainer.train_gan` keep sequences of their own.
 """
 from __future__ import print_function, absolute_import
 
@@ -18,20 +22,15 @@ import inspect
 import time
 
 import torch
-from rg_hip.tape import backward as _backward
 import torch.nn as nn
 
-from rg_hip import functional as RF, search
+from rg_hip import functional as RF, hostloop
+from rg_hip.hostloop import AverageMeter
 from rg_hip.nn import invalidate_folds
 from rg_hip.parallel import GradReducer, attach_stage_hooks
+from rg_hip.tape import backward as _backward
 
 from .utils.data.diff_augs import my_transform
-from .utils.meters import AverageMeter
-
-try:                                    # optional observability, never on the hot path
-    import wandb as _wandb
-except Exception:                       # pragma: no cover
-    _wandb = None
 
 
 def _first(out):
@@ -71,67 +70,48 @@ def intra_cl(q, k, temperature, group_size=16):
     return RF.cross_entropy_rows(grouped, targets, 1.0 / temperature)
 
 
-class ClusterContrastTrainer(object):
+class _EncoderTrainer(object):
+    """What the two encoder trainers share: the reducer cache, the parsing of a ReID batch, the forward, and the epoch of
+    `train_iters` draws from an IterLoader on the shell of rg_hip.hostloop."""
+
     def __init__(self, encoder, memory=None):
-        super(ClusterContrastTrainer, self).__init__()
+        super(_EncoderTrainer, self).__init__()
         self.encoder = encoder
         self.memory = memory
         self.sync_every_step = False
         self._reducers = _ReducerCache()
 
-    def train(self, epoch, data_loader, optimizer, print_freq=10, train_iters=400, acc_iters=0):
+    def _epoch(self, epoch, data_loader, step, print_freq, train_iters, tail="", wandb_key=None):
         self.encoder.train()
+        hostloop.run_epoch(epoch, (data_loader.next() for _ in range(train_iters)), train_iters, len(data_loader), step,
+                           print_freq, self.sync_every_step, tail=tail, wandb_key=wandb_key)
 
-        batch_time = AverageMeter()
-        data_time = AverageMeter()
-        losses = AverageMeter()
-        pending = []
-
-        end = time.time()
-        for i in range(train_iters):
-            inputs = data_loader.next()
-            data_time.update(time.time() - end)
-
-            inputs, labels, indexes = self._parse_data(inputs)
-            loss = self.step(inputs, labels, optimizer)
-
-            pending.append(loss)
-            if self.sync_every_step or (i + 1) % print_freq == 0 or i + 1 == train_iters:
-                for v in torch.stack(pending).tolist():     # one device->host transfer for the interval
-                    losses.update(v)
-                pending = []
-
-            batch_time.update(time.time() - end)
-            end = time.time()
-
-            if (i + 1) % print_freq == 0:
-                print('Epoch: [{}][{}/{}]\t'
-                      'Time {:.3f} ({:.3f})\t'
-                      'Data {:.3f} ({:.3f})\t'
-                      'Loss {:.3f} ({:.3f})'
-                      .format(epoch, i + 1, len(data_loader),
-                              batch_time.val, batch_time.avg,
-                              data_time.val, data_time.avg,
-                              losses.val, losses.avg))
-
-    def step(self, inputs, labels, optimizer):
-        """One training step (reference loop body :229-244); returns the detached device loss."""
-        self._reducers.get(optimizer, self.encoder)       # replicas are synchronised (rank-0 broadcast) BEFORE the first forward
-        f_out = _first(self._forward(inputs))
-        loss = RF.weighted_mean(self.memory(f_out, labels))
-        optimizer.zero_grad()
-        _backward(loss)
-        self._reducers.get(optimizer, self.encoder).reduce()
-        optimizer.step()
-        return loss.detach()
+    def _reducer(self, optimizer):
+        """called BEFORE a step's forward: creating the reducer synchronises the replicas (rank-0 broadcast)"""
+        return self._reducers.get(optimizer, self.encoder)
 
     def _parse_data(self, inputs):
         imgs, _, pids, _, indexes = inputs
-        dev = search.device()
-        return imgs.to(dev, non_blocking=True), pids.to(dev, non_blocking=True), indexes.to(dev, non_blocking=True)
+        return hostloop.to_device(imgs, pids, indexes)
 
-    def _forward(self, inputs):
-        return self.encoder(inputs)
+    def _forward(self, inputs, fuse=True):
+        if fuse:
+            return self.encoder(inputs)
+        return self.encoder(inputs, fuse=fuse)
+
+
+class ClusterContrastTrainer(_EncoderTrainer):
+    def train(self, epoch, data_loader, optimizer, print_freq=10, train_iters=400, acc_iters=0):
+        def step(inputs):
+            inputs, labels, indexes = self._parse_data(inputs)
+            return self.step(inputs, labels, optimizer)
+        self._epoch(epoch, data_loader, step, print_freq, train_iters)
+
+    def step(self, inputs, labels, optimizer):
+        """One training step (reference loop body :229-244); returns the detached device loss."""
+        reducer = self._reducer(optimizer)
+        f_out = _first(self._forward(inputs))
+        return hostloop.update(RF.weighted_mean(self.memory(f_out, labels)), optimizer, reducer)
 
 
 class ClusterContrastPartTrainer(ClusterContrastTrainer):
@@ -155,32 +135,23 @@ class ClusterContrastPartTrainer(ClusterContrastTrainer):
         self.T = temperature
 
     def step(self, inputs, labels, optimizer):
-        reducer = self._reducers.get(optimizer, self.encoder)     # replicas are synchronised (rank-0 broadcast) BEFORE the first forward
+        reducer = self._reducer(optimizer)
         f_g, f_p1, f_p2, f_gc = self._forward(inputs)
         terms = [RF.weighted_mean(self.memory(f_gc, labels))]
         for f in (f_p1, f_p2, f_g):
             terms.append(RF.weighted_mean(intra_cl(f, f.detach(), self.T, self.group_size)))
-        loss = RF._WeightedSum.apply(torch.stack(terms), None, 1.0)
-        optimizer.zero_grad()
-        _backward(loss)
-        reducer.reduce()
-        optimizer.step()
-        return loss.detach()
+        return hostloop.update(RF._WeightedSum.apply(torch.stack(terms), None, 1.0), optimizer, reducer)
 
 
-class ClusterContrastWithGANTrainer(object):
+class ClusterContrastWithGANTrainer(_EncoderTrainer):
     def __init__(self, encoder, GAN=None, writer=None, memory=None, opt=None):
-        super(ClusterContrastWithGANTrainer, self).__init__()
-        self.encoder = encoder
+        super(ClusterContrastWithGANTrainer, self).__init__(encoder, memory)
         if GAN is None:
             raise TypeError('GAN not implemented!')       # the reference's `raise('...')` is a TypeError too
         self.gan = GAN
-        self.memory = memory
         self.memoryb = memory
         self.writer = writer
         self.f_metric = nn.L1Loss()
-        self.sync_every_step = False
-        self._reducers = _ReducerCache()
         if opt is not None:
             self.opt = opt
             self.T = opt.cl_temp
@@ -191,64 +162,32 @@ class ClusterContrastWithGANTrainer(object):
         """`joint=None` follows trainers.py:129-187 when the GAN has no generator loss API and the joint step of
         trainers_b.py:617-814 when it has (`synthesize_p`, `get_loss_G`, `backward_D`)."""
         print("train both gan and reid")
-        self.encoder.train()
         if joint is None:
             joint = all(hasattr(self.gan, a) for a in ("synthesize_p", "get_loss_G", "backward_D", "optimizer_G",
                                                        "optimizer_D"))
-        batch_time = AverageMeter()
-        data_time = AverageMeter()
-        losses = AverageMeter()
-        pending = []
-        end = time.time()
 
-        for i in range(train_iters):
-            inputs = data_loader.next()
-            data_time.update(time.time() - end)
-
+        def step(inputs):
             reid_inputs, labels, indexes = self._parse_data(inputs[0])
             self.gan.set_input(inputs[1])
             if joint:
-                loss = self.joint_step(reid_inputs, labels, indexes, optimizer, conf_weight)
-            else:
-                self._reducers.get(optimizer, self.encoder)
-                out = self._forward(reid_inputs)
-                f_out = _first(out)
-                f_gan = out[1] if isinstance(out, (tuple, list)) else None
-                loss_ori = self.memory(f_out, labels, gan_inputs=None if f_gan is None else f_gan.detach())
-                loss = RF.weighted_mean(loss_ori)
-                optimizer.zero_grad()
-                _backward(loss)
-                self._reducers.get(optimizer, self.encoder).reduce()
-                optimizer.step()
-                loss = loss.detach()
+                return self.joint_step(reid_inputs, labels, indexes, optimizer, conf_weight)
+            return self._reid_only_step(reid_inputs, labels, optimizer)
+        self._epoch(epoch, data_loader, step, print_freq, train_iters, tail="\n", wandb_key="total_loss")
 
-            pending.append(loss)
-            if self.sync_every_step or (i + 1) % print_freq == 0 or i + 1 == train_iters:
-                for v in torch.stack(pending).tolist():
-                    losses.update(v)
-                    if _wandb is not None and getattr(_wandb, "run", None) is not None:
-                        _wandb.log({"total_loss": v})
-                pending = []
-
-            batch_time.update(time.time() - end)
-            end = time.time()
-
-            if (i + 1) % print_freq == 0:
-                print('Epoch: [{}][{}/{}]\t'
-                      'Time {:.3f} ({:.3f})\t'
-                      'Data {:.3f} ({:.3f})\t'
-                      'Loss {:.3f} ({:.3f})\n'
-                      .format(epoch, i + 1, len(data_loader),
-                              batch_time.val, batch_time.avg,
-                              data_time.val, data_time.avg,
-                              losses.val, losses.avg))
+    def _reid_only_step(self, reid_inputs, labels, optimizer):
+        """the cluster-contrast update of trainers.py:129-187; the encoder's second output, if any, goes to the memory detached"""
+        reducer = self._reducer(optimizer)
+        out = self._forward(reid_inputs)
+        f_gan = out[1] if isinstance(out, (tuple, list)) else None
+        loss_ori = self.memory(_first(out), labels, gan_inputs=None if f_gan is None else f_gan.detach())
+        return hostloop.update(RF.weighted_mean(loss_ori), optimizer, reducer)
 
     def joint_step(self, reid_inputs, labels, indexes, optimizer, conf_weight=None):
         """Joint ReID + GAN step, live lines of trainers_b.py:657-774: encode -> synthesize from the detached
         feature -> generator loss (D frozen) + confidence-weighted cluster-contrast loss -> D step -> one backward
         through G and the encoder -> both optimizers step."""
         gan = self.gan
-        self._reducers.get(optimizer, self.encoder)       # rank-0 broadcast before the first forward, not after its backward
+        reducer = self._reducer(optimizer)                # rank-0 broadcast before the first forward, not after its backward
         out = self._forward(reid_inputs)
         f_out = _first(out)
         # train-mode encoders return (bn_x, normalize(feature map)) (CC/clustercontrast/models/resnet.py:107); the
@@ -270,7 +209,7 @@ class ClusterContrastWithGANTrainer(object):
         gan.optimizer_G.zero_grad()
         optimizer.zero_grad()
         _backward(loss)
-        self._reducers.get(optimizer, self.encoder).reduce()
+        reducer.reduce()
         gan.optimizer_G.step()
         optimizer.step()
         return loss.detach()
@@ -292,15 +231,10 @@ class ClusterContrastWithGANTrainer(object):
         n = reid_inputs.shape[0]
         if group_size <= 0 or n % group_size:
             raise ValueError("hard_mix_step: a batch of %d is not whole identity groups of %d" % (n, group_size))
-        reducer = self._reducers.get(optimizer, self.encoder)     # rank-0 broadcast before the first forward
+        reducer = self._reducer(optimizer)
         f_out = _first(self._forward(reid_inputs))
         f_ex = self._embed_hard_mix(f_out.detach(), group_size)
-        loss = self.memory(f_out, labels, ex_f=f_ex)
-        optimizer.zero_grad()
-        _backward(loss)
-        reducer.reduce()
-        optimizer.step()
-        return loss.detach()
+        return hostloop.update(self.memory(f_out, labels, ex_f=f_ex), optimizer, reducer)
 
     def _embed_hard_mix(self, f_out, group_size):
         """eval-mode embeddings of the GAN's hard-mixed images [identities, D], detached (trainers.py:66-70)"""
@@ -334,7 +268,7 @@ class ClusterContrastWithGANTrainer(object):
             reid_inputs, labels, _ = self._parse_data(inputs[0])
             self.gan.set_input(inputs[1])
             return self.hard_mix_step(reid_inputs, labels, optimizer, group_size)
-        self._loop(epoch, data_loader, step, print_freq, train_iters, log="reid_loss", tail="\n")
+        self._epoch(epoch, data_loader, step, print_freq, train_iters, tail="\n", wandb_key="reid_loss")
 
     def train_reid(self, epoch, data_loader, optimizer, print_freq=10, train_iters=400, acc_iters=0):
         """The ReID warm-up loop, trainers_b.py:1087-1138: `loss = memory(f_out, labels)` on the ReID half `inputs[0]` of every
@@ -345,57 +279,13 @@ class ClusterContrastWithGANTrainer(object):
 
         def step(inputs):
             reid_inputs, labels, _ = self._parse_data(inputs[0])
-            reducer = self._reducers.get(optimizer, self.encoder)
-            loss = self.memory(_first(self._forward(reid_inputs)), labels)
-            if loss.dim():
-                loss = RF.weighted_mean(loss)
-            optimizer.zero_grad()
-            _backward(loss)
-            reducer.reduce()
-            optimizer.step()
-            return loss.detach()
-        self._loop(epoch, data_loader, step, print_freq, train_iters)
+            return self._warm_up_step(reid_inputs, labels, optimizer)
+        self._epoch(epoch, data_loader, step, print_freq, train_iters)
 
-    def _loop(self, epoch, data_loader, step, print_freq, train_iters, log=None, tail=""):
-        """the loop shell of `train` / `train_reid`: meters, the deferred `loss.item()` (one transfer per print interval unless
-        `sync_every_step`), the reference's print line"""
-        self.encoder.train()
-        batch_time = AverageMeter()
-        data_time = AverageMeter()
-        losses = AverageMeter()
-        pending = []
-        end = time.time()
-        for i in range(train_iters):
-            inputs = data_loader.next()
-            data_time.update(time.time() - end)
-            pending.append(step(inputs))
-            if self.sync_every_step or (i + 1) % print_freq == 0 or i + 1 == train_iters:
-                for v in torch.stack(pending).tolist():
-                    losses.update(v)
-                    if log is not None and _wandb is not None and getattr(_wandb, "run", None) is not None:
-                        _wandb.log({log: v})
-                pending = []
-            batch_time.update(time.time() - end)
-            end = time.time()
-            if (i + 1) % print_freq == 0:
-                print('Epoch: [{}][{}/{}]\t'
-                      'Time {:.3f} ({:.3f})\t'
-                      'Data {:.3f} ({:.3f})\t'
-                      'Loss {:.3f} ({:.3f})'
-                      .format(epoch, i + 1, len(data_loader),
-                              batch_time.val, batch_time.avg,
-                              data_time.val, data_time.avg,
-                              losses.val, losses.avg) + tail)
-
-    def _parse_data(self, inputs):
-        imgs, _, pids, _, indexes = inputs
-        dev = search.device()
-        return imgs.to(dev, non_blocking=True), pids.to(dev, non_blocking=True), indexes.to(dev, non_blocking=True)
-
-    def _forward(self, inputs, fuse=True):
-        if fuse:
-            return self.encoder(inputs)
-        return self.encoder(inputs, fuse=fuse)
+    def _warm_up_step(self, reid_inputs, labels, optimizer):
+        reducer = self._reducer(optimizer)
+        loss = self.memory(_first(self._forward(reid_inputs)), labels)
+        return hostloop.update(RF.weighted_mean(loss) if loss.dim() else loss, optimizer, reducer)
 
     def intra_cl(self, q, k, group_size=16):
         """group contrast of trainers.py:200-210 at this trainer's temperature (the module-level `intra_cl`)."""
@@ -436,8 +326,7 @@ class GANTrainer(object):
             batch_time.update(time.time() - end)
             end = time.time()
             if (i + 1) % print_freq == 0:
-                if _wandb is not None and getattr(_wandb, "run", None) is not None:
-                    _wandb.log({"GANLoss_G": gan_losses['G'], "GANLoss_D": gan_losses['D']})
+                hostloop.wandb_log({"GANLoss_G": gan_losses['G'], "GANLoss_D": gan_losses['D']})
                 print('Epoch: [{}][{}/{}]\t'
                       'Time {:.3f} ({:.3f})\t'
                       'Data {:.3f} ({:.3f})\t'

@@ -14,13 +14,15 @@ top-k gallery rows of ALL queries are gathered into one [Q * k, 2048] operand an
 Device-resident counterparts under names of their own, which need no reference tree: `extract_features_device`,
 `evaluate_all_device` and `DeviceCascadeEvaluator`.  Its second stage gathers the pairs inside `ops.pair_score`
 (csrc/cascade.hip: no [Q * k, 2048] operand is ever built) and merges in place on the device with `ops.cascade_merge`.
+The collection loop behind `extract_features_device` is rg_hip/hostloop.py's and the opening of `evaluate_all_device` is
+`clustercontrast.evaluators.score_mean_ap`.
 """
 from __future__ import print_function, absolute_import
 
 import numpy as np
 import torch
 
-from rg_hip import ops, search
+from rg_hip import hostloop, ops, search
 
 
 def pairwise_distance(features, query=None, gallery=None, metric=None):
@@ -116,35 +118,7 @@ def softmax_class0(x):
 def extract_features_device(model, data_loader, print_freq=1):
     """The reference's `extract_features` loop (:46-73) with the features kept on the device: (DeviceFeatures, labels).  Reads
     the first three fields of a batch (imgs, fnames, pids), so the 4-tuples of this package's loaders and 5-tuples both work."""
-    import time
-    from collections import OrderedDict
-    from clustercontrast.evaluators import DeviceFeatures
-    from clustercontrast.utils.meters import AverageMeter
-    model.eval()
-    batch_time, data_time = AverageMeter(), AverageMeter()
-    blocks, index, labels = [], OrderedDict(), OrderedDict()
-    dev, base = search.device(), 0
-    end = time.time()
-    with torch.no_grad():
-        for i, batch in enumerate(data_loader):
-            imgs, fnames, pids = batch[0], batch[1], batch[2]
-            data_time.update(time.time() - end)
-            outputs = model(torch.as_tensor(imgs).to(dev, non_blocking=True)).data
-            blocks.append(outputs.reshape(outputs.shape[0], -1))
-            for j, (fname, pid) in enumerate(zip(fnames, pids)):
-                index[fname] = base + j
-                labels[fname] = pid
-            base += outputs.shape[0]
-            batch_time.update(time.time() - end)
-            end = time.time()
-            if (i + 1) % print_freq == 0:
-                print('Extract Features: [{}/{}]\t'
-                      'Time {:.3f} ({:.3f})\t'
-                      'Data {:.3f} ({:.3f})\t'
-                      .format(i + 1, len(data_loader),
-                              batch_time.val, batch_time.avg,
-                              data_time.val, data_time.avg))
-    return DeviceFeatures(torch.cat(blocks, 0), index), labels
+    return hostloop.collect_features(model, data_loader, print_freq)
 
 
 def evaluate_all_device(distmat, query=None, gallery=None,
@@ -158,17 +132,9 @@ def evaluate_all_device(distmat, query=None, gallery=None,
     sampling: with dataset=None and with dataset='cuhk03' a run without the reference tree ends in that function's
     NotImplementedError (after the 'Mean AP' line)."""
     from clustercontrast.evaluation_metrics import ranking as R
-    if query is not None and gallery is not None:
-        query_ids = [pid for _, pid, _ in query]
-        gallery_ids = [pid for _, pid, _ in gallery]
-        query_cams = [cam for _, _, cam in query]
-        gallery_cams = [cam for _, _, cam in gallery]
-    else:
-        assert (query_ids is not None and gallery_ids is not None
-                and query_cams is not None and gallery_cams is not None)
-    res = R._score(distmat, query_ids, gallery_ids, query_cams, gallery_cams, 100, False)
-    mAP = float(res["ap_sum"] / res["num_valid"])
-    print('Mean AP: {:4.1%}'.format(mAP))
+    from clustercontrast.evaluators import score_mean_ap
+    res, mAP, (query_ids, gallery_ids, query_cams, gallery_cams) = score_mean_ap(distmat, query, gallery, query_ids, gallery_ids,
+                                                                                 query_cams, gallery_cams)
     if not top1:
         return mAP
 

@@ -6,7 +6,8 @@ clustercontrast/trainers.py documents):
   * host->device copies are non-blocking and go to `rg_hip.search.device()`;
   * loss and precision stay on the device and reach the meters once per print interval (`loss.data[0]`, a device sync per step
     in the reference, :34) unless `sync_every_step=True`;
-  * `step(imgs1, imgs2, targets, optimizer)` is the loop body, `train` a loop over it;
+  * `step(imgs1, imgs2, targets, optimizer)` is the loop body, `train` a loop over it: the epoch loop, the update tail of a step
+    and the batch's host->device copy are rg_hip/hostloop.py's, shared with clustercontrast/trainers.py;
   * `_forward` runs SiameseNet.forward_loss — both trunk passes, the verification head, nn.CrossEntropyLoss() and `accuracy` as
     one tape program with the head on csrc/verif_head.hip — when the model is a SiameseNet (bare or as `.module` of a
     DataParallel wrapper) whose embed model has BatchNorm and classifier, and the criterion is an nn.CrossEntropyLoss with default
@@ -22,15 +23,10 @@ above 1 the trainer raises before the first forward.
 """
 from __future__ import print_function, absolute_import
 
-import time
-
-import torch
 import torch.distributed as dist
 from torch import nn
 
-from clustercontrast.utils.meters import AverageMeter
-from rg_hip import parallel, search
-from rg_hip.tape import backward as _backward
+from rg_hip import hostloop, parallel
 
 from .evaluation_metrics import accuracy
 from .models.multi_branch import SiameseNet
@@ -54,42 +50,12 @@ class BaseTrainer(object):
     def train(self, epoch, data_loader, optimizer, base_lr=0.1, print_freq=1):
         self.model.train()
 
-        batch_time = AverageMeter()
-        data_time = AverageMeter()
-        losses = AverageMeter()
-        precisions = AverageMeter()
-        pending = []
-        n_batches = len(data_loader)
-
-        end = time.time()
-        for i, inputs in enumerate(data_loader):
-            data_time.update(time.time() - end)
-
+        def step(inputs):
             inputs, targets = self._parse_data(inputs)
-            loss, prec1 = self.step(inputs[0], inputs[1], targets, optimizer)
-
-            pending.append((torch.stack([loss, prec1]), targets.size(0)))
-            if self.sync_every_step or (i + 1) % print_freq == 0 or i + 1 == n_batches:
-                vals = torch.stack([p for p, _ in pending]).tolist()        # one device->host transfer for the interval
-                for (lv, pv), (_, n) in zip(vals, pending):
-                    losses.update(lv, n)
-                    precisions.update(pv, n)
-                pending = []
-
-            batch_time.update(time.time() - end)
-            end = time.time()
-
-            if (i + 1) % print_freq == 0:
-                print('Epoch: [{}][{}/{}]\t'
-                      'Time {:.3f} ({:.3f})\t'
-                      'Data {:.3f} ({:.3f})\t'
-                      'Loss {:.3f} ({:.3f})\t'
-                      'Prec {:.2%} ({:.2%})\t'
-                      .format(epoch, i + 1, n_batches,
-                              batch_time.val, batch_time.avg,
-                              data_time.val, data_time.avg,
-                              losses.val, losses.avg,
-                              precisions.val, precisions.avg))
+            return self.step(inputs[0], inputs[1], targets, optimizer), targets.size(0)
+        n_batches = len(data_loader)
+        hostloop.run_epoch(epoch, data_loader, n_batches, n_batches, step, print_freq, self.sync_every_step,
+                           columns=hostloop.LOSS + (("Prec", "{:.2%} ({:.2%})"),), tail="\t")
 
     def step(self, imgs1, imgs2, targets, optimizer):
         """One training step (reference loop body :32-39); returns the detached device (loss, prec), both 0-d."""
@@ -98,10 +64,7 @@ class BaseTrainer(object):
                 "reid.trainers: stage I under torch.distributed is not built — a SiameseNet in train mode runs its trunk twice on "
                 "one tape, which the stage-hook gradient reducer does not reduce correctly (ADVICE.md item 1); run one process")
         loss, prec1 = self._forward([imgs1, imgs2], targets)
-        optimizer.zero_grad()
-        _backward(loss)
-        optimizer.step()
-        return loss.detach(), prec1.detach().reshape(())
+        return hostloop.update(loss, optimizer), prec1.detach().reshape(())
 
     def _parse_data(self, inputs):
         raise NotImplementedError
@@ -113,9 +76,8 @@ class BaseTrainer(object):
 class SiameseTrainer(BaseTrainer):
     def _parse_data(self, inputs):
         (imgs1, _, pids1, _), (imgs2, _, pids2, _) = inputs
-        dev = search.device()
-        targets = (pids1 == pids2).long().to(dev, non_blocking=True)
-        return [imgs1.to(dev, non_blocking=True), imgs2.to(dev, non_blocking=True)], targets
+        targets, imgs1, imgs2 = hostloop.to_device((pids1 == pids2).long(), imgs1, imgs2)
+        return [imgs1, imgs2], targets
 
     def _siamese(self):
         """the SiameseNet whose fused program `_forward` may take, or None"""
