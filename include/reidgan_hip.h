@@ -787,6 +787,39 @@ int rg_flip_pad_crop(const float* x, const int* params, const float* pad_value, 
  * erases only channel 0 of non-RGB inputs). */
 int rg_erase_rects(float* x, const int* rects, const float* fill, int N, int C, int H, int W, rg_stream_t stream);
 
+/* ---- device-resident image bank (csrc/databank.hip): finished fp32 NCHW batches gathered from uint8 planes in HBM ----
+ * The reference's host pipeline (CC/examples/cluster_contrast_gan_train_usl_infomap.py:71-186, preprocessor.py:99-199) resizes
+ * every image deterministically BEFORE any random draw, so the resized uint8 planes are built once and kept on the device:
+ * Market-1501 (35 585 images) is 3.5 GB at 256x128 plus 0.9 GB at 128x64, MSMT17 (126 441 images) 12.4 + 3.1 GB, of 288 GB.
+ * Each entry is ONE launch, uses no workspace, no atomic and no intermediate batch, and reads per sample n the bank row idx[n].
+ * idx and the draws are made on the host; the Python wrappers (rg_hip/ops/databank.py) refuse every out-of-range value before
+ * the launch.  The kernels additionally read nothing for an index outside [0, M) (such a sample is written as padding / zeros).
+ *
+ * rg_bank_reid_batch: bank_u8[M][Hs][Ws][3] interleaved RGB bytes; params[N][8] int32 = (flip, top, left, er0, ec0, eh, ew,
+ * reserved); lut[3][256] = ToTensor + Normalize of every byte value per channel, ((b / 255) - mean[c]) / std[c] computed by
+ * the caller in fp32; fill[3] = RandomErasing's per-channel value.  The reference's order is Pad(pad, black) ->
+ * RandomCrop((H, W)) -> ToTensor -> Normalize -> RandomErasing -> torch.flip(img, [2]); for out[n][c][y][x]:
+ *     xs = flip ? W-1-x : x                                   (the rectangle and the crop are in PRE-flip coordinates)
+ *     eh > 0 and (y, xs) in [er0, er0+eh) x [ec0, ec0+ew)  -> fill[c]
+ *     (r, q) = (top + y - pad, left + xs - pad) outside the stored plane -> lut[c][0]   (normalised black)
+ *     otherwise                                            -> lut[c][bank_u8[idx[n]][r][q][c]]
+ * No floating-point arithmetic happens on the device, so the batch equals the host pipeline's bit for bit.  The test-time
+ * transform (Resize -> ToTensor -> Normalize) is pad = 0, (H, W) = (Hs, Ws) and all-zero params.  Output rows are written with
+ * 16-byte stores where W % 4 == 0, element by element otherwise. */
+int rg_bank_reid_batch(const unsigned char* bank_u8, int M, int Hs, int Ws, const int* idx, const int* params, const float* lut,
+                       const float* fill, float* out, int N, int H, int W, int pad, rg_stream_t stream);
+/* The GAN branch's image (preprocessor.py:145-175, `Xs`): out[n][c][y][x] = lut[c][bank_u8[idx[n]][y][flip ? Wg-1-x : x][c]] from
+ * a second plane set [M][Hg][Wg][3] with its own table (Normalize((.5,.5,.5), (.5,.5,.5))).  The flip of sample n is
+ * flip[n * flip_stride], so column 0 of the ReID entry's params serves with flip_stride = 8. */
+int rg_bank_gan_batch(const unsigned char* bank_u8, int M, int Hg, int Wg, const int* idx, const int* flip, int flip_stride,
+                      const float* lut, float* out, int N, rg_stream_t stream);
+/* The GAN branch's pose maps (`obtain_bone` + torch.flip(Ps, [2])): out[N][J][Hg][Wg] = rg_pose_maps mode 1 of the centres
+ * centres[idx[n]][J][2] = (row, col) (INT32_MIN: missing joint -> zero map), one sigma for all, read at (y, flip ? Wg-1-x : x);
+ * bit-equal to rg_pose_maps(mode 1) on the gathered centres followed by the flip.  The centres are computed once per image
+ * when the bank is built (the reference recomputes them from a pandas row per draw). */
+int rg_bank_pose_batch(const int* centres, int M, int J, const int* idx, const int* flip, int flip_stride, float sigma, float* out,
+                       int N, int Hg, int Wg, rg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

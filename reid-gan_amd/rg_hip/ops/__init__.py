@@ -23,6 +23,7 @@ unit(s) it calls.
     optimizer  csrc/optim.hip
     profile    the launch profiler
     datagen    csrc/datagen.hip: on-device input synthesis
+    databank   csrc/databank.hip: batches gathered from the device-resident uint8 image bank, the host-checked draws
 
 The names are re-exported BY VALUE, which is safe because shared state (_DEV, CAPTURE_GEN, CAPTURING, _SIDE, _ws_sizes, _HANDED,
 _INLINE_SIDE, _CONST_FILL, _CLOCK, _PROFILING) is created in exactly one submodule and only ever mutated in place, and the RG_*
@@ -70,6 +71,7 @@ from .kmeans import (KMEANS_MAX_N, KMEANS_MAX_K, KMEANS_MAX_D, kmeans_rand_perm,
 from .optimizer import adam_advance, adam_step_dev, adam_step, sgd_step
 from .profile import profile_enable, check_not_profiling, profile_reset, profile_collect
 from .datagen import pose_maps, flip_pad_crop, erase_rects_
+from .databank import bank_lut, BankDraws, bank_draws, bank_reid_batch, bank_gan_batch, bank_pose_batch
 
 # ---- underscore names that code outside the package reads (rg_hip.nn / netgraph / parallel / lowp, the tests, tools/) ------------
 from ._base import _stream, _p, _chk, _pair, _ws_query, _ws_sizes
@@ -88,3 +90,4 @@ from .retrieval import _pair_vec
 from .dbscan import _chk_dbscan_matrix, _chk_dbscan_lists, _nbr_ptr
 from .infomap import _chk_infomap_table, _chk_infomap_graph, _infomap_level, _infomap_aggregate
 from .kmeans import _chk_kmeans_shape, _row_sqsum
+from .databank import _chk_bank, _chk_draws, _chk_lut

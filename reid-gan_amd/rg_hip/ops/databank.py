@@ -1,0 +1,170 @@
+"""Device-resident image bank (csrc/databank.hip): finished fp32 batches gathered from uint8 planes that stay in HBM.
+
+The indices and the augmentation draws are made on the host.  `bank_draws` packs them into ONE int32 host buffer (params [N, 8]
+followed by idx [N]) that crosses to the device in one copy; the three batch wrappers check the HOST copy against the geometry
+they are about to launch with and raise ValueError before anything is enqueued — a bad draw never reaches the device."""
+from __future__ import absolute_import
+
+import torch
+
+from ._base import _chk, _chk_rr, _p, _stream, lib
+
+
+def bank_lut(mean, std):
+    """[3, 256] fp32 host table: ToTensor + Normalize of every byte value, in exactly the reference's arithmetic
+    (`img.float().div(255)` then `sub_(mean).div_(std)`, both in fp32)."""
+    v = torch.arange(256, dtype=torch.float32).div(255)
+    m = torch.as_tensor(mean, dtype=torch.float32).view(-1, 1)
+    s = torch.as_tensor(std, dtype=torch.float32).view(-1, 1)
+    if m.numel() != 3 or s.numel() != 3:
+        raise ValueError("bank_lut: three means and three standard deviations expected")
+    return v.view(1, 256).sub(m).div(s).contiguous()
+
+
+class BankDraws(object):
+    """One batch's bank rows and draws: `idx` int32 [N] and `params` int32 [N, 8] = (flip, top, left, er0, ec0, eh, ew, 0) as
+    views of one host buffer, and (after `to`) the same two views of its single device copy."""
+
+    __slots__ = ("host", "idx", "params", "idx_dev", "params_dev", "_ok")
+
+    def __init__(self, idx, params):
+        idx = torch.as_tensor(idx).reshape(-1)
+        n = idx.numel()
+        if n == 0:
+            raise ValueError("bank_draws: an empty batch")
+        if idx.is_cuda or idx.dtype not in (torch.int32, torch.int64):
+            raise ValueError("bank_draws: idx must be a host tensor of int32 / int64 (the draws are checked on the host)")
+        if n and (int(idx.min()) < -2 ** 31 or int(idx.max()) >= 2 ** 31):
+            raise ValueError("bank_draws: idx does not fit int32")
+        host = self.host = torch.zeros(n * 9, dtype=torch.int32)
+        self.params, self.idx = host[:n * 8].view(n, 8), host[n * 8:]
+        self.idx.copy_(idx)
+        if params is not None:
+            params = torch.as_tensor(params)
+            if params.is_cuda or params.dtype not in (torch.int32, torch.int64) or params.dim() != 2 or params.shape[0] != n \
+                    or params.shape[1] not in (7, 8):
+                raise ValueError("bank_draws: params must be a host integer tensor [N, 7] or [N, 8]")
+            if params.numel() and (int(params.min()) < -2 ** 31 or int(params.max()) >= 2 ** 31):
+                raise ValueError("bank_draws: params do not fit int32")
+            self.params[:, :params.shape[1]].copy_(params)
+        self.idx_dev = self.params_dev = None
+        self._ok = set()
+
+    def to(self, device):
+        """the one host->device copy of the batch"""
+        n = self.idx.numel()
+        dev = self.host.to(device, non_blocking=True)
+        self.params_dev, self.idx_dev = dev[:n * 8].view(n, 8), dev[n * 8:]
+        return self
+
+    def check(self, who, M, geometry=None):
+        """ValueError unless 0 <= idx < M, flip in {0, 1} and, with geometry = (Hs, Ws, H, W, pad), 0 <= top <= 2 pad + Hs - H,
+        0 <= left <= 2 pad + Ws - W and every rectangle (eh > 0) has ew > 0 and lies inside [0, H) x [0, W)."""
+        key = (M, geometry)
+        if key in self._ok:
+            return
+        idx, p = self.idx, self.params
+        if int(idx.min()) < 0 or int(idx.max()) >= M:
+            raise ValueError("%s: bank row index outside [0, %d)" % (who, M))
+        if bool(((p[:, 0] != 0) & (p[:, 0] != 1)).any()):
+            raise ValueError("%s: flip must be 0 or 1" % who)
+        if geometry is not None:
+            Hs, Ws, H, W, pad = geometry
+            if bool(((p[:, 1] < 0) | (p[:, 1] > 2 * pad + Hs - H)).any()):
+                raise ValueError("%s: top outside [0, %d]" % (who, 2 * pad + Hs - H))
+            if bool(((p[:, 2] < 0) | (p[:, 2] > 2 * pad + Ws - W)).any()):
+                raise ValueError("%s: left outside [0, %d]" % (who, 2 * pad + Ws - W))
+            er0, ec0, eh, ew = p[:, 3].long(), p[:, 4].long(), p[:, 5].long(), p[:, 6].long()
+            if bool((eh < 0).any()) or bool((ew < 0).any()):
+                raise ValueError("%s: negative erase rectangle size" % who)
+            on = eh > 0
+            if bool((on & ((ew <= 0) | (er0 < 0) | (ec0 < 0) | (er0 + eh > H) | (ec0 + ew > W))).any()):
+                raise ValueError("%s: erase rectangle outside the %dx%d output" % (who, H, W))
+        self._ok.add(key)
+
+
+def bank_draws(idx, params=None, device=None):
+    """BankDraws of host `idx` [N] and `params` [N, 8] (None: all zero, the test-time transform), uploaded when `device` is given."""
+    d = BankDraws(idx, params)
+    return d if device is None else d.to(device)
+
+
+def _chk_bank(who, bank_u8):
+    if not torch.is_tensor(bank_u8) or bank_u8.dtype != torch.uint8 or bank_u8.dim() != 4 or bank_u8.shape[3] != 3:
+        raise ValueError("%s: the bank must be a uint8 tensor [M, H, W, 3]" % who)
+    return _chk_rr(bank_u8, "bank", dtype=torch.uint8, dim=4)
+
+
+def _chk_draws(who, draws, device):
+    if not isinstance(draws, BankDraws):
+        raise TypeError("%s: draws must come from ops.bank_draws (they are checked on the host before the launch)" % who)
+    if draws.idx_dev is None:
+        draws.to(device)
+    if draws.idx_dev.device != device:
+        raise RuntimeError("%s: the draws were uploaded to %s, the bank lives on %s" % (who, draws.idx_dev.device, device))
+    return draws
+
+
+def _chk_lut(who, lut):
+    lut = _chk(lut, "lut")
+    if tuple(lut.shape) != (3, 256):
+        raise ValueError("%s: lut must be [3, 256]" % who)
+    return lut
+
+
+def bank_reid_batch(bank_u8, draws, lut, fill, out_hw, pad=0):
+    """[N, 3, H, W] fp32: Pad(pad) -> RandomCrop((H, W)) -> ToTensor -> Normalize -> RandomErasing -> flip of the bank rows
+    draws.idx with draws.params [N, 8] = (flip, top, left, er0, ec0, eh, ew, -); one launch (rg_bank_reid_batch)."""
+    bank_u8 = _chk_bank("bank_reid_batch", bank_u8)
+    M, Hs, Ws = bank_u8.shape[0], bank_u8.shape[1], bank_u8.shape[2]
+    H, W = int(out_hw[0]), int(out_hw[1])
+    pad = int(pad)
+    if pad < 0 or H <= 0 or W <= 0 or H > Hs + 2 * pad or W > Ws + 2 * pad:
+        raise ValueError("bank_reid_batch: crop %dx%d does not fit the %dx%d plane padded by %d" % (H, W, Hs, Ws, pad))
+    draws = _chk_draws("bank_reid_batch", draws, bank_u8.device)
+    draws.check("bank_reid_batch", M, (Hs, Ws, H, W, pad))
+    lut = _chk_lut("bank_reid_batch", lut)
+    fill = _chk(fill, "fill")
+    if fill.numel() != 3:
+        raise ValueError("bank_reid_batch: three fill values expected")
+    N = draws.idx.numel()
+    out = torch.empty((N, 3, H, W), dtype=torch.float32, device=bank_u8.device)
+    lib.rg_bank_reid_batch(_p(bank_u8), M, Hs, Ws, _p(draws.idx_dev), _p(draws.params_dev), _p(lut), _p(fill), _p(out), N, H, W, pad,
+                           _stream())
+    return out
+
+
+def bank_gan_batch(bank_u8, draws, lut):
+    """[N, 3, Hg, Wg] fp32: ToTensor -> Normalize -> flip of the bank rows draws.idx (flip = draws.params[:, 0]); one launch."""
+    bank_u8 = _chk_bank("bank_gan_batch", bank_u8)
+    M, Hg, Wg = bank_u8.shape[0], bank_u8.shape[1], bank_u8.shape[2]
+    draws = _chk_draws("bank_gan_batch", draws, bank_u8.device)
+    draws.check("bank_gan_batch", M)
+    lut = _chk_lut("bank_gan_batch", lut)
+    N = draws.idx.numel()
+    out = torch.empty((N, 3, Hg, Wg), dtype=torch.float32, device=bank_u8.device)
+    lib.rg_bank_gan_batch(_p(bank_u8), M, Hg, Wg, _p(draws.idx_dev), _p(draws.params_dev), 8, _p(lut), _p(out), N, _stream())
+    return out
+
+
+def bank_pose_batch(centres, draws, height, width, sigma=6.0):
+    """[N, J, Hg, Wg] fp32 pose maps of the bank rows draws.idx from the int32 centre table [M, J, 2] (INT32_MIN: missing joint),
+    flipped where draws.params[:, 0] is set: pose_maps(mode=1) + flip_images on the gathered centres, in one launch."""
+    if not torch.is_tensor(centres) or centres.dtype != torch.int32 or centres.dim() != 3 or centres.shape[2] != 2:
+        raise ValueError("bank_pose_batch: centres must be an int32 tensor [M, J, 2]")
+    centres = _chk_rr(centres, "centres", dtype=torch.int32, dim=3)
+    M, J = centres.shape[0], centres.shape[1]
+    height, width = int(height), int(width)
+    if not (0 < height <= 1024 and 0 < width <= 1024):
+        raise ValueError("bank_pose_batch: map size must be within 1024x1024")
+    if not float(sigma) > 0:
+        raise ValueError("bank_pose_batch: sigma must be positive")
+    draws = _chk_draws("bank_pose_batch", draws, centres.device)
+    draws.check("bank_pose_batch", M)
+    N = draws.idx.numel()
+    if N > 65535:
+        raise ValueError("bank_pose_batch: at most 65535 samples per launch")
+    out = torch.empty((N, J, height, width), dtype=torch.float32, device=centres.device)
+    lib.rg_bank_pose_batch(_p(centres), M, J, _p(draws.idx_dev), _p(draws.params_dev), 8, float(sigma), _p(out), N, height, width,
+                           _stream())
+    return out
