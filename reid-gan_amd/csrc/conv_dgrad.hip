@@ -575,12 +575,7 @@ static DgradShape dgrad_classes(const ConvGeom& g, DgradClass* cls) {
     for (int ah = 0; ah < g.SH; ++ah)
         for (int aw = 0; aw < g.SW; ++aw) {
             DgradClass& cl = cls[ah * g.SW + aw];
-            cl.r0 = (ah + g.PH) % g.SH;
-            cl.s0 = (aw + g.PW) % g.SW;
-            cl.nrh = cl.r0 < g.KH ? (g.KH - cl.r0 + g.SH - 1) / g.SH : 0;
-            cl.nrw = cl.s0 < g.KW ? (g.KW - cl.s0 + g.SW - 1) / g.SW : 0;
-            cl.Hc = ah < g.H ? (g.H - ah + g.SH - 1) / g.SH : 0;
-            cl.Wc = aw < g.W ? (g.W - aw + g.SW - 1) / g.SW : 0;
+            static_cast<ParityClass&>(cl) = parity_class(g, ah, aw);
             cl.Ngc = g.N * cl.Hc * cl.Wc;
             cl.Kgc = g.K * cl.nrh * cl.nrw;
             cl.d_taps = make_fastdiv(cl.nrh * cl.nrw);

@@ -34,6 +34,8 @@
 // measured choice with its file cache, the test knobs and the split-K arrival registry.  The kernels and the entry points that launch
 // them are in conv_fwd.hip, conv_dgrad.hip and conv_wgrad.hip, on the shared device code of conv_core.h (arithmetic, loaders,
 // epilogues), conv_halo.h (tap-reuse 3x3), conv_finish.h (split-K finishers), conv_thin.h and conv_planes.h (bf16-plane kernels).
+// conv_prims.h (dividers, XCD remap, buffer access) and conv_reduce.h (the split-K slab sum of the weight gradients) are shared with
+// the fp8 units, conv_f8.hip and f8_quant.hip, which also take ConvGeom and the stride-parity classes from conv_plan.h.
 #include "conv_plan.h"
 
 #include <stdio.h>
@@ -58,8 +60,6 @@ const Switches& switches() {
     return s;
 }
 
-static bool fits_buffer(int64_t elems) { return elems > 0 && elems * 4 < (1ll << 31); }
-
 int validate(const char* op, const ConvGeom& g) {
     const int N = g.N, C = g.C, H = g.H, W = g.W, K = g.K, KH = g.KH, KW = g.KW, SH = g.SH, SW = g.SW, PH = g.PH, PW = g.PW, P = g.P, Q = g.Q;
     RG_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && K > 0 && KH > 0 && KW > 0, "%s: non-positive dimension", op);
@@ -71,8 +71,8 @@ int validate(const char* op, const ConvGeom& g) {
                    (int64_t)C * H * W < (1ll << 31) && (int64_t)K * P * Q < (1ll << 31) &&
                    (int64_t)K * KH * KW < (1ll << 31),
                "%s: dimension product exceeds 2^31", op);
-    RG_REQUIRE(fits_buffer((int64_t)N * C * H * W) && fits_buffer((int64_t)N * K * P * Q) &&
-                   fits_buffer((int64_t)K * C * KH * KW),
+    RG_REQUIRE(fits_buffer((int64_t)N * C * H * W * 4) && fits_buffer((int64_t)N * K * P * Q * 4) &&
+                   fits_buffer((int64_t)K * C * KH * KW * 4),
                "%s: every tensor must be smaller than 2 GiB (32-bit buffer offsets)", op);
     return RG_OK;
 }

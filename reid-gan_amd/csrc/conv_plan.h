@@ -1,7 +1,7 @@
 // Host side of the fp32 convolution library that the family units (conv_fwd.hip, conv_dgrad.hip, conv_wgrad.hip) share: the
-// geometry of a call, the tile / split-K plan, the switches and the measured choice.  Everything declared here is defined ONCE, in
-// conv_igemm.hip, which also owns the state behind it (the choice table and its file, the pick knob, the forced plan / plane mask,
-// the split-K arrival registry).  No device code: the planner compiles without a kernel.
+// geometry of a call (conv_f8.hip uses it too), the tile / split-K plan, the switches and the measured choice.  Everything declared
+// here is defined ONCE, in conv_igemm.hip, which also owns the state behind it (the choice table and its file, the pick knob, the
+// forced plan / plane mask, the split-K arrival registry).  No device code: the planner compiles without a kernel.
 #pragma once
 #include "rg_common.h"
 
@@ -24,6 +24,24 @@ inline double alg_bytes(const ConvGeom& g) {
     return 4.0 * ((double)g.N * g.C * g.H * g.W + (double)g.K * g.C * g.KH * g.KW + (double)g.N * g.K * g.P * g.Q);
 }
 int validate(const char* op, const ConvGeom& g);
+// a tensor of this many bytes can sit behind one buffer resource (32-bit byte offsets, OOB = 2^31)
+inline bool fits_buffer(int64_t bytes) { return bytes > 0 && bytes < (1ll << 31); }
+
+// Stride-parity class (ah, aw) of a data gradient: the input pixels (ah + SH hc, aw + SW wc), Hc x Wc of them per image, receive
+// the filter taps (r0 + SH j, s0 + SW jj), nrh x nrw of them.  A stride-1 layer has the one class (0, 0): every pixel, every tap.
+struct ParityClass {
+    int r0, s0, nrh, nrw, Hc, Wc;
+};
+inline ParityClass parity_class(const ConvGeom& g, int ah, int aw) {
+    ParityClass c;
+    c.r0 = (ah + g.PH) % g.SH;
+    c.s0 = (aw + g.PW) % g.SW;
+    c.nrh = c.r0 < g.KH ? (g.KH - c.r0 + g.SH - 1) / g.SH : 0;
+    c.nrw = c.s0 < g.KW ? (g.KW - c.s0 + g.SW - 1) / g.SW : 0;
+    c.Hc = ah < g.H ? (g.H - ah + g.SH - 1) / g.SH : 0;
+    c.Wc = aw < g.W ? (g.W - aw + g.SW - 1) / g.SW : 0;
+    return c;
+}
 
 // the caller's scratch
 struct Workspace {

@@ -4,6 +4,7 @@
 // rg_conv2d_wgrad_workspace, rg_weights_to_krsc, rg_weights_to_krsc_multi.
 #define RG_PLANES_WGRAD
 #include "conv_thin.h"
+#include "conv_reduce.h"
 
 namespace {
 
@@ -435,26 +436,12 @@ __global__ __launch_bounds__(NT) void conv_wgrad_kernel(const ConvP p) {
 }
 
 // dw[i] = sum_s ws[s][i]; with rsc != 0 the partial columns are (r,s)-major (n' = rs*C + c) and are written back in
-// the checkpoint order [K][C][RS].  Deterministic (fixed summation tree).  64 outputs x 4 split lanes per
-// workgroup: small filter tensors with hundreds of splits stay parallel instead of one long serial chain per thread.
+// the checkpoint order [K][C][RS].  Deterministic: the fixed summation tree of conv_reduce.h.
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ ws, float* __restrict__ out,
                                                             int64_t n, int splits, int rsc, int C, int RS) {
-    __shared__ float red[4][64];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int64_t i = (int64_t)blockIdx.x * 64 + tx;
-    float s0 = 0.f, s1 = 0.f;
-    if (i < n) {
-        int k = ty;
-        for (; k + 4 < splits; k += 8) {
-            s0 += ws[(int64_t)k * n + i];
-            s1 += ws[(int64_t)(k + 4) * n + i];
-        }
-        if (k < splits) s0 += ws[(int64_t)k * n + i];
-    }
-    red[ty][tx] = s0 + s1;
-    __syncthreads();
-    if (ty != 0 || i >= n) return;
-    const float s = (red[0][tx] + red[1][tx]) + (red[2][tx] + red[3][tx]);
+    int64_t i;
+    float s;
+    if (!splitk_sum(ws, n, splits, i, s)) return;
     if (!rsc) {
         out[i] = s;
         return;
@@ -466,42 +453,12 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     out[m * crs + (int64_t)c * RS + rs] = s;
 }
 
-// n % 4 == 0: 64 float4 outputs x 4 split lanes per workgroup, four slab loads in flight per thread; per element the same summation
-// tree as splitk_reduce_kernel (lane ty adds splits ty, ty + 8, ... and ty + 4, ty + 12, ... in two chains): same values.
+// n % 4 == 0: float4 outputs, per element the values of splitk_reduce_kernel
 __global__ __launch_bounds__(256) void splitk_reduce_vec_kernel(const float* __restrict__ ws, float* __restrict__ out, int64_t n,
                                                                 int splits, int rsc, int C, int RS) {
-    __shared__ float4 red[4][64];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int64_t n4 = n >> 2;
-    const int64_t i = (int64_t)blockIdx.x * 64 + tx;
-    const float4* w4 = reinterpret_cast<const float4*>(ws);
-    float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
-    if (i < n4) {
-        int k = ty;
-        for (; k + 12 < splits; k += 16) {
-            const float4 a = w4[(int64_t)k * n4 + i], b = w4[(int64_t)(k + 4) * n4 + i];
-            const float4 c = w4[(int64_t)(k + 8) * n4 + i], d = w4[(int64_t)(k + 12) * n4 + i];
-            s0.x += a.x; s0.y += a.y; s0.z += a.z; s0.w += a.w;
-            s1.x += b.x; s1.y += b.y; s1.z += b.z; s1.w += b.w;
-            s0.x += c.x; s0.y += c.y; s0.z += c.z; s0.w += c.w;
-            s1.x += d.x; s1.y += d.y; s1.z += d.z; s1.w += d.w;
-        }
-        for (; k + 4 < splits; k += 8) {
-            const float4 a = w4[(int64_t)k * n4 + i], b = w4[(int64_t)(k + 4) * n4 + i];
-            s0.x += a.x; s0.y += a.y; s0.z += a.z; s0.w += a.w;
-            s1.x += b.x; s1.y += b.y; s1.z += b.z; s1.w += b.w;
-        }
-        if (k < splits) {
-            const float4 a = w4[(int64_t)k * n4 + i];
-            s0.x += a.x; s0.y += a.y; s0.z += a.z; s0.w += a.w;
-        }
-    }
-    red[ty][tx] = make_float4(s0.x + s1.x, s0.y + s1.y, s0.z + s1.z, s0.w + s1.w);
-    __syncthreads();
-    if (ty != 0 || i >= n4) return;
-    const float4 r0 = red[0][tx], r1 = red[1][tx], r2 = red[2][tx], r3 = red[3][tx];
-    const float4 v = make_float4((r0.x + r1.x) + (r2.x + r3.x), (r0.y + r1.y) + (r2.y + r3.y), (r0.z + r1.z) + (r2.z + r3.z),
-                                 (r0.w + r1.w) + (r2.w + r3.w));
+    int64_t i;
+    float4 v;
+    if (!splitk_sum4(ws, n, splits, i, v)) return;
     if (!rsc) {
         reinterpret_cast<float4*>(out)[i] = v;
         return;
@@ -520,8 +477,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_vec_kernel(const float* __r
 
 // Split-K reduction of the weight gradient of a convolution whose frozen-statistics BatchNorm is folded into it (norm_fold.hip, "conv +
 // frozen-statistics BatchNorm"): ONE workgroup per filter row k sums the slabs of its row (float4 columns, the summation tree of
-// splitk_reduce_vec_kernel: same G bit for bit), and finishes the fold while G is in registers — dgamma[k] = invstd (sum_m W G - mean
-// sum g), dbeta[k] = sum g (from the slice partials), dW = scale[k] G.  Replaces splitk_reduce_vec_kernel + bn_fold_wgrad_kernel:
+// splitk_reduce_vec_kernel, conv_reduce.h, written out here inside the row loop: same G bit for bit), and finishes the fold while G
+// is in registers — dgamma[k] = invstd (sum_m W G - mean sum g), dbeta[k] = sum g (from the slice partials), dW = scale[k] G.  Replaces splitk_reduce_vec_kernel + bn_fold_wgrad_kernel:
 // one launch, one write and one read of G less per folded layer (106 layers per FD-GAN step).  M % 4 == 0, 16-byte aligned buffers.
 __global__ __launch_bounds__(256) void splitk_reduce_fold_kernel(const float* __restrict__ ws, float* __restrict__ out,
                                                                  const float* __restrict__ w, int M, int64_t n, int splits,

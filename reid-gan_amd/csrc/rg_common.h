@@ -63,6 +63,7 @@ struct ProfScope {
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+static inline int pad16(int v) { return (v + 15) / 16 * 16; }      // channel / batch counts of the fp8 operand layouts
 
 // workgroups of 256 threads for a grid-stride kernel over `items`, between 1 and the unit's cap
 static inline unsigned grid_for(int64_t items, int64_t cap) {

@@ -194,6 +194,41 @@ def test_conv_f8_against_emulation_and_fp32(dev, geom):
     assert _l2rel(dw, wr.grad) <= TOL_BWD_VS_FP32
 
 
+# N, C, H, W, K, k, stride, pad; splits of the plan; the reducer K*C*k*k selects.  Every geometry of GEOMS has K*C*k*k % 4 == 0
+# and at most two splits, so the scalar reducer and the deep loops of both never run there.
+WGRAD_SPLIT_GEOMS = [
+    ((2, 5, 8, 8, 3, 3, 1, 1), 2),        # 135 outputs: scalar reducer
+    ((2, 5, 21, 21, 3, 3, 1, 1), 13),     # scalar, 111 k-tiles in 13 splits of 9: both chains and the tail of lane 0
+    ((2, 5, 21, 21, 4, 3, 1, 1), 13),     # 180 outputs: float4 reducer, the four-loads-in-flight loop (k + 12 < splits)
+]
+
+
+@pytest.mark.parametrize("geom,splits", WGRAD_SPLIT_GEOMS)
+def test_wgrad_split_k_reducers(dev, geom, splits):
+    """The weight gradient alone against the emulation where the split-K slab sum (csrc/conv_reduce.h) has work to do.  Only
+    TOL_EMU: the fp32 bands were measured on layers with >= 16 channels."""
+    from rg_hip import lowp, ops
+    N, C, H, W, K, k, s, p = geom
+    P, Q = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+    n = K * C * k * k
+    assert ops._ws_query("rg_conv2d_f8_wgrad_workspace", N, C, K, k, k, P, Q) == splits * n * 4      # the regime meant
+    g = torch.Generator().manual_seed(N * 1000 + C + K)
+    x = torch.randn(N, C, H, W, generator=g)
+    dy = torch.randn(N, K, P, Q, generator=g) * 1e-3
+    st, states = _states(dev)
+    sx, sdy = states[0], states[1]
+    xd, dyd = x.to(dev), dy.to(dev)
+    sx.prepare(xd)
+    xqt = lowp.quantize(xd, sx, "chwn")
+    sdy.prepare(dyd)
+    dyqt = lowp.quantize(dyd, sdy, "chwn")
+    dw = lowp.conv_wgrad(xqt, dyqt, (N, C, H, W, K, k, k, s, s, p, p))
+    dw_emu = R.conv_wgrad(x, dy, (K, C, k, k), 0, 1, s, p)
+    err = _maxrel(dw, dw_emu)
+    print("wgrad vs emulation %.3e (n = %d, %d splits)" % (err, n, splits))
+    assert err <= TOL_EMU, "wgrad vs emulation %.3e" % err
+
+
 def test_transposed_conv_roles(dev):
     """ConvTranspose2d(3x3, stride 2, padding 1, output_padding 1) of the generator's decoder blocks: forward = data gradient
     with e4m3 activations, input gradient = forward kernel with an e5m2 operand, filter gradient with swapped roles."""

@@ -26,9 +26,10 @@ FAMILY = {
     "conv_fwd_pl_kernel": CONV, "conv_dgrad_pl_kernel": CONV, "conv_wgrad_pl_kernel": CONV,
     # norm_fold.hip: conv helpers of the folded (frozen-statistics) BatchNorm
     "bn_fold_wgrad_kernel": CONV, "fold_filters_multi_kernel": CONV, "bn_fold_kernel": CONV,
-    # conv_f8.hip
-    "conv_f8_kernel": CONV_F8, "f8_amax_kernel": CONV_F8, "f8_quantize_dual_kernel": CONV_F8,
-    "f8_quantize_transpose_kernel": CONV_F8, "f8_roll_kernel": CONV_F8, "f8_splitk_reduce_kernel": CONV_F8, "f8_splitk_reduce_vec_kernel": CONV_F8,
+    # conv_f8.hip: the fp8 GEMMs and their split-K reducers
+    "conv_f8_kernel": CONV_F8, "f8_splitk_reduce_kernel": CONV_F8, "f8_splitk_reduce_vec_kernel": CONV_F8,
+    # f8_quant.hip: scaling states and quantisers
+    "f8_amax_kernel": CONV_F8, "f8_quantize_dual_kernel": CONV_F8, "f8_quantize_transpose_kernel": CONV_F8, "f8_roll_kernel": CONV_F8,
     # norm_bn.h (instantiated by norm_bn.hip and norm_dsbn.hip), norm_bn.hip
     "bn_apply_fwd_kernel": "norm", "bn_bwd_apply_kernel": "norm",
     "bn_bwd_reduce_finalize_kernel": "norm", "bn_bwd_reduce_partial_kernel": "norm", "bn_eval_bwd_fused_kernel": "norm",
