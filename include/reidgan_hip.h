@@ -51,8 +51,8 @@ int rg_profile_collect(double* ms, double* flops, double* bytes, long long* call
 
 /* ---- convolution: implicit GEMM, fp32 tensors, split-bf16 arithmetic on v_mfma_f32_32x32x16_bf16 ----
  * (every fp32 operand is split exactly into three bf16 pieces and each product evaluated as the six partial products of weight
- * >= 2^-16 with fp32 accumulation: the error model of an fp32 FMA chain, csrc/conv_igemm.hip and conv_core.h; -DRG_MATH=1 builds the fp32-MFMA
- * v_mfma_f32_32x32x2_f32 arithmetic of rounds 1-2).  Overflow is NOT fp32's: an operand that is +-Inf, or finite but above the
+ * >= 2^-16 with fp32 accumulation: the error model of an fp32 FMA chain, csrc/conv_igemm.hip and conv_core.h).
+ * Overflow is NOT fp32's: an operand that is +-Inf, or finite but above the
  * largest bf16 (|x| >= 3.3961e38: its leading piece rounds to Inf), makes its products NaN (Inf - Inf in the split) where an fp32
  * FMA chain would give +-Inf; nothing in the reference's training range comes within 30 orders of magnitude of that)
  * Replaces nn.Conv2d / nn.ConvTranspose2d of the ResNet-50 trunk (CC/clustercontrast/models/
@@ -99,7 +99,7 @@ int rg_weights_to_krsc_multi(const void* table, int count, int total_blocks, rg_
 int rg_conv_set_force(int tile, int splits);
 /* development knob: bit mask of the conv kernel families that run on the bf16-plane operand path of csrc/conv_planes.h (operands
  * split into their bf16 pieces once, on the way into LDS) instead of the default kernels: 1 forward, 2 data gradient, 4 weight
- * gradient, 8: with a family bit, the eight-wave form of the 128 x 128 tile (same as RG_CONV_PL); identical results up to fp32
+ * gradient, 8: with a family bit, the eight-wave form of the 128 x 128 tile; identical results up to fp32
  * summation order.  Returns the previous mask. */
 int rg_conv_set_planes(int mask);
 /* The generic fwd / dgrad / wgrad kernels exist in two implementations (default kernels and the plane path above); unless one is
@@ -113,7 +113,7 @@ int rg_conv_tune_stats(int* out);
  * 64 / 128 / 256 tile / split-K plan (fwd / dgrad / wgrad).  index >= 0 pins that kind: every choice of the kind runs candidate
  * min(index, ncand - 1) at once (before the plane-path mask and RG_CONV_TUNE are consulted), without measuring, synchronising or
  * recording anything (rg_conv_tune_stats and the cache file are untouched); -1 releases it.  It pins choices, it does not create
- * them: with RG_CONV_TUNE=0 / RG_CONV_TUNE_PLAN=0 a geometry has one plan and no path choice.  Returns the previous index (-1: not
+ * them: with RG_CONV_TUNE=0 a geometry has one plan and no path choice.  Returns the previous index (-1: not
  * pinned), or a value below -1 for an unknown kind / an index below -1 (rg_last_error).  Off by default. */
 int rg_conv_set_pick(int kind, int index);
 /* while any kind is pinned, every choice appends one record of 18 ints: the 16 key fields, its candidate count and the index that

@@ -10,16 +10,9 @@ namespace {
 
 using rg::conv::BK;
 using rg::conv::ConvGeom;
-#ifndef RG_MATH
-#define RG_MATH 3       // 3: split-bf16 arithmetic (three bf16 pieces per fp32 operand, six MFMA products); 1: fp32 MFMA (below)
-#endif
 #ifndef RG_WAVES
-#if RG_MATH == 3
-#define RG_WAVES 3      // the split fragments (3 x 4 registers per 32 x 16 operand block) need the 168-register budget
-#else
-#define RG_WAVES 4      // waves per SIMD the fwd / dgrad kernels are compiled for (register budget 512 / RG_WAVES; 4 = 128
-                        // registers: 2-5 spilled dwords outside the k-loop, +0.8 % on the step over 3)
-#endif
+#define RG_WAVES 3      // waves per SIMD the fwd / dgrad kernels are compiled for (register budget 512 / RG_WAVES): the split
+                        // fragments (3 x 4 registers per 32 x 16 operand block) need the 168-register budget
 #endif
 constexpr int LPAD = 4;
 constexpr int NT = 256;
@@ -86,7 +79,7 @@ struct Tile {
 };
 
 // ---- matrix arithmetic of one 16-deep k-tile -------------------------------------------------------------------------------
-// RG_MATH 3 (default): fp32 operands are split EXACTLY into three bf16 pieces each (x = hi + mid + lo with hi = bf16(x),
+// fp32 operands are split EXACTLY into three bf16 pieces each (x = hi + mid + lo with hi = bf16(x),
 // mid = bf16(x - hi), lo = x - hi - mid, each rounded to nearest even: the residuals are exact fp32 subtractions and the last one
 // has at most 8 significant bits, so it is a bf16 number; rounding rather than truncating keeps the residuals' signs independent
 // of the operand's, so the dropped terms below do not add up to a bias — a truncating split underestimates every product by
@@ -96,9 +89,8 @@ struct Tile {
 // on v_mfma_f32_32x32x16_bf16 (bf16 x bf16 products are exact in fp32, accumulation in fp32).  The three dropped products
 // (mid*lo, lo*mid, lo*lo) are <= 2^-23 |a b| together: one fp32 rounding per product, i.e. the error model of the fp32 FMA chain
 // the fp32 MFMA evaluates — measured against fp64 in tests/test_ops_gpu.py — at 6/16 of its matrix-pipe time (the bf16 MFMA
-// issues 16x the FLOPs per cycle).  The split runs on the VALU after the fragment's ds_read_b32s (LDS tiles stay fp32, k-major,
-// shared with RG_MATH 1), 4.5 VALU ops per element; small terms are accumulated first.
-// RG_MATH 1: v_mfma_f32_32x32x2_f32 (a k-ordered fp32 fma chain), the round-1/2 arithmetic.
+// issues 16x the FLOPs per cycle).  The split runs on the VALU after the fragment's ds_read_b32s (LDS tiles stay fp32, k-major),
+// 4.5 VALU ops per element; small terms are accumulated first.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef int int4r __attribute__((ext_vector_type(4)));
 
@@ -152,7 +144,6 @@ __device__ __forceinline__ void mma_split3(const Split3& a, const Split3& b, flo
 #define RG_PIN()
 #endif
 
-#if RG_MATH == 3
 // One 16-deep k-step of a (TM x 32) x (TN x 32) wave tile from fp32 operands in LDS: ra(i, q) / rb(j, q) read element q (k index
 // 8 * (lane >> 5) + q) of this lane's row of A block i / column of B block j.
 // Software-pipelined by hand: the matrix pipe and the VALU do not overlap across the waves of a SIMD here (the co-resident
@@ -199,7 +190,6 @@ __device__ __forceinline__ void mma_kstep(RA ra, RB rb, floatx16 (&acc)[TM][TN])
             c = mfma_bf16(a[i].hi, b[j].hi, c);
         }
 }
-#endif
 
 // One 16-deep k-tile of MFMAs.  `hook(q)`, q = 0..3, is called behind the last matrix instructions: the kernels use it to write
 // the NEXT tile's staged registers into the other LDS buffer, so those ds_writes (and the vmcnt wait in front of them) issue in
@@ -208,30 +198,10 @@ template <typename T, typename Hook>
 __device__ __forceinline__ void mma_tile(const float (*As)[T::LDA], const float (*Bs)[T::LDB],
                                          floatx16 (&acc)[T::TM][T::TN], int wm, int wn, int lane, Hook hook) {
     const int l32 = lane & 31, kh = lane >> 5;
-#if RG_MATH == 3
     static_assert(BK == 16, "one bf16 MFMA k-step per LDS tile");
     mma_kstep<T::TM, T::TN>([&](int i, int q) { return As[8 * kh + q][wm * T::WTM + i * 32 + l32]; },
                             [&](int j, int q) { return Bs[8 * kh + q][wn * T::WTN + j * 32 + l32]; }, acc);
     hook(0); hook(1); hook(2); hook(3);
-#else
-#pragma unroll
-    for (int ks = 0; ks < BK / 2; ++ks) {
-        const int k = 2 * ks + kh;
-        float a[T::TM], b[T::TN];
-#pragma unroll
-        for (int i = 0; i < T::TM; ++i) a[i] = As[k][wm * T::WTM + i * 32 + l32];
-#pragma unroll
-        for (int j = 0; j < T::TN; ++j) b[j] = Bs[k][wn * T::WTN + j * 32 + l32];
-#pragma unroll
-        for (int i = 0; i < T::TM; ++i)
-#pragma unroll
-            for (int j = 0; j < T::TN; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
-        // stores of the next tile behind the LAST k-step: the global loads issued at the top of the tile get 7/8 of its
-        // matrix work as cover before their first use
-        if (ks == BK / 2 - 1) { hook(0); hook(1); hook(2); hook(3); }
-    }
-#endif
 }
 
 // true when element e of a CNT-element staging array belongs to quarter q (q < 0: every quarter)

@@ -563,7 +563,7 @@ struct DgradShape {
     int64_t ng_eff, kg_eff;      // columns of the classes with taps, their mean depth
     int64_t ng_total;            // columns of all classes: one partial row of a strided split-K launch
     double flops;
-    // Strided classes may split their reductions too (RG_DGRAD_STRIDED_SPLIT=0: never): the 3x3 / 1x1 stride-2 layers of layer3 /
+    // Strided classes may split their reductions too: the 3x3 / 1x1 stride-2 layers of layer3 /
     // layer4 have 32-128 tiles for 256 CUs and class depths that differ 4x (1, 2, 2 and 4 taps); every class is cut into the same
     // number of splits of ITS depth, the partial columns of the classes lie side by side and conv_splitk_finish_strided_kernel
     // scatters the sums to the classes' pixels with the fused epilogue.
@@ -593,7 +593,7 @@ static DgradShape dgrad_classes(const ConvGeom& g, DgradClass* cls) {
             }
         }
     s.kg_eff = s.ng_eff > 0 ? (int64_t)(kw_sum / (double)s.ng_eff) : s.kg_max;
-    s.ssplit = switches().strided_split != 0 && s.ng_eff > 0 && (int64_t)g.C * g.N * g.H * g.W < (1ll << 31);
+    s.ssplit = s.ng_eff > 0 && (int64_t)g.C * g.N * g.H * g.W < (1ll << 31);
     return s;
 }
 // the depth a strided launch is planned on (see above)
@@ -655,7 +655,7 @@ static int dgrad_smallc(const DgradCall& c) {
         const int gi = g.N * rg::cdiv(dp.cls[i].Hc, 4) * dp.cls[i].Wc;
         if (gi > gmax) gmax = gi;
     }
-    if (few_taps && switches().smallc_px && gmax > 0)          // RG_SMALLC_PX=0: the plain kernel
+    if (few_taps && gmax > 0)
         hipLaunchKernelGGL((conv_dgrad_smallc_px_kernel<4>), dim3(((rg::cdiv(gmax, 256) + 7) / 8) * 8 * ncls), dim3(256), lds, c.stream,
                            dp);
     else
@@ -706,8 +706,8 @@ static int dgrad_run_plan(const DgradCall& c, Plan pl) {
             else { RG_DGRAD_PL_LAUNCH(64, 128, 2, 4); }
         } else if (impl) {
             RG_TILE_SWITCH(pl.tile, RG_DGRAD_PL_LAUNCH);
-        } else if (mode == 2 && switches().dma && (pl.tile == 0 || pl.tile == 1) && g.C % 4 == 0) {
-            // 1x1 / stride 1: both operands are lane-linear in memory -> LDS-DMA ring (conv1x1_dma_kernel; RG_CONV_DMA=0: never)
+        } else if (mode == 2 && (pl.tile == 0 || pl.tile == 1) && g.C % 4 == 0) {
+            // 1x1 / stride 1: both operands are lane-linear in memory -> LDS-DMA ring (conv1x1_dma_kernel)
             if (pl.tile == 0) hipLaunchKernelGGL((conv1x1_dma_kernel<128>), grid, dim3(NT), 0, stream, dp);
             else hipLaunchKernelGGL((conv1x1_dma_kernel<64>), grid, dim3(NT), 0, stream, dp);
         } else {
@@ -770,7 +770,7 @@ int dgrad_impl(const ConvGeom& g, const DgradOps& o, const Workspace& ws, hipStr
         // the tap-reuse kernel and the generic kernels compete per geometry, as in the forward pass — with fused row sums only
         // when the generic plan writes the same row-sum columns (their count is the caller's contract with the planning query:
         // both unsplit on 128-pixel tiles with two wave columns -> the same column per (n-tile, wave column))
-        bool can_tune = path_tune_enabled();
+        bool can_tune = tune_enabled();
         if (can_tune && o.ep.rowsum) {
             int gcols = -1;
             can_tune = dgrad_impl(g, DgradOps(), Workspace(), nullptr, &gcols, false) == RG_OK && gcols == cols;

@@ -12,7 +12,7 @@
 //   * block tile BM x 128 x 64 bytes, 4 wave64 as 2 x 2, 32x32x64 MFMA tiles (one k-tile = one MFMA step per 32x32 block); LDS rows are 64 bytes with the 16-byte chunk
 //     index XOR-swizzled by (row >> 2) & 3, which makes both the ds_write_b128 staging stores and the ds_read_b128 fragment
 //     reads conflict-free; two ds_read_b128 per operand row feed one MFMA (lanes 0-31 take bytes 0-31 of the row, lanes 32-63
-//     bytes 32-63, identically for both operands); double-buffered LDS, one barrier per k-tile, next tile's loads in flight during the MFMAs;
+//     bytes 32-63, identically for both operands); a four-deep LDS-DMA ring, one barrier per k-tile, the next three tiles' loads in flight during the MFMAs.
 #include "conv_plan.h"
 #include "conv_prims.h"
 #include "conv_reduce.h"
@@ -26,6 +26,7 @@ using rg::pad16;
 constexpr int NT = 256;
 constexpr int BN = 128;
 constexpr int ROWB = 64;                     // bytes of one LDS row = one k-tile
+constexpr int NB = 4;                        // LDS buffers of the DMA ring: NB - 1 k-tiles in flight per workgroup
 
 // ---------------------------------------------------------------------------------------------------------------
 // GEMM core
@@ -70,13 +71,13 @@ __device__ __forceinline__ floatx16 mfma8(int8v a, int8v b, floatx16 c) {
 __device__ __forceinline__ unsigned lds_off(int row, int chunk) { return (unsigned)row * ROWB + (unsigned)((chunk ^ (row >> 2)) & 3) * 16u; }
 
 // MODE 0 forward, 1 data gradient (class from the workgroup id, see below), 2 weight gradient (blockIdx.z = split)
-// NB = 2: operands staged through registers (global -> VGPR -> ds_write), two LDS buffers, prefetch distance one k-tile.
-// NB > 2: LDS-DMA ring (buffer_load ... lds, 16 bytes per lane): no staging registers, NB - 1 k-tiles in flight per workgroup.  A
-//         k-tile is only 64 reduction bytes = one MFMA step per 32x32 block (~100 ns of matrix work per workgroup), so the loop is
-//         bound by load LATENCY, not by issue: the ring plus 2-3 resident workgroups keeps ~10 tiles per CU in flight.
+// Operands reach LDS through an LDS-DMA ring (buffer_load ... lds, 16 bytes per lane): no staging registers, NB - 1 k-tiles in flight
+// per workgroup.  A k-tile is only 64 reduction bytes = one MFMA step per 32x32 block (~100 ns of matrix work per workgroup), so the
+// loop is bound by load LATENCY, not by issue: the ring plus 2-3 resident workgroups keeps ~10 tiles per CU in flight (the first
+// version, a register-staged two-buffer loop, was measured slower: profiles/retired_switches.txt).
 typedef __attribute__((address_space(3))) void lds_void_t;
 
-template <int MODE, int BM, int FA, int FB, int NB>
+template <int MODE, int BM, int FA, int FB>
 __global__ __launch_bounds__(NT) void conv_f8_kernel(const F8P p) {
     constexpr int WTM = BM / 2, WTN = BN / 2;
     constexpr int TM = WTM / 32, TN = WTN / 32;
@@ -159,7 +160,6 @@ __global__ __launch_bounds__(NT) void conv_f8_kernel(const F8P p) {
         }
     }
 
-    int4v sa_[AR], sb_[2];
     floatx16 acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(NT) void conv_f8_kernel(const F8P p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-    // byte offsets (or OOB) of the 16-byte chunks this thread stages for k-tile kt; `chx` = its chunk of the 64-byte row
+    // byte offsets (or OOB) of the 16-byte chunks this thread fetches for k-tile kt; `chx` = its chunk of the 64-byte row
     auto tile_offsets = [&](int kt, int chx, unsigned (&oa)[AR], unsigned (&ob)[2]) {
         const int q = kt * 4 + chx;                // chunk index along the reduction
         const bool qok = q < Kc;
@@ -207,14 +207,6 @@ __global__ __launch_bounds__(NT) void conv_f8_kernel(const F8P p) {
             }
         }
     };
-    auto load_tile = [&](int kt) {
-        unsigned oa[AR], ob[2];
-        tile_offsets(kt, ch, oa, ob);
-#pragma unroll
-        for (int i = 0; i < AR; ++i) sa_[i] = bload16(ra, oa[i]);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) sb_[i] = bload16(rb, ob[i]);
-    };
     // LDS-DMA: lane l of wave w lands at (w*64 + l) * 16 bytes of the 4 KiB pass = row w*16 + l/4, physical chunk l%4, so the lane
     // fetches the LOGICAL chunk whose swizzled position that is (the XOR is an involution); out-of-range chunks arrive as zeros
     const int che = ch ^ ((srow >> 2) & 3);
@@ -229,12 +221,6 @@ __global__ __launch_bounds__(NT) void conv_f8_kernel(const F8P p) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (lds_void_t*)(base + BM * ROWB + i * 4096), 16, (int)ob[i], 0, 0, 0);
-    };
-    auto store_tile = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < AR; ++i) *reinterpret_cast<int4v*>(&lds[buf][lds_off(srow + 64 * i, ch)]) = sa_[i];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) *reinterpret_cast<int4v*>(&lds[buf][BM * ROWB + lds_off(srow + 64 * i, ch)]) = sb_[i];
     };
 
     const int nk = (Kc + 3) >> 2;
@@ -265,43 +251,26 @@ __global__ __launch_bounds__(NT) void conv_f8_kernel(const F8P p) {
 #pragma unroll
                 for (int j = 0; j < TN; ++j) acc[i][j] = mfma8<FA, FB>(a[i], b[j], acc[i][j]);
     };
-    if (NB == 2) {
-        if (kt_begin < kt_end) {
-            load_tile(kt_begin);
-            store_tile(0);
-        }
-        __syncthreads();
-        int cur = 0;
-        for (int kt = kt_begin; kt < kt_end; ++kt) {
-            const bool has_next = kt + 1 < kt_end;
-            if (has_next) load_tile(kt + 1);
-            compute_tile(lds[cur], lds[cur] + BM * ROWB);
-            if (has_next) store_tile(cur ^ 1);
-            __syncthreads();
-            cur ^= 1;
-        }
-    } else {
-        constexpr int LPT = AR + 2;                // DMA instructions per thread and k-tile
-        const int nkt = kt_end - kt_begin;
+    constexpr int LPT = AR + 2;                    // DMA instructions per thread and k-tile
+    const int nkt = kt_end - kt_begin;
 #pragma unroll
-        for (int sidx = 0; sidx < NB - 1; ++sidx)
-            if (sidx < nkt) dma_tile(kt_begin + sidx, sidx);
-        int buf = 0;
-        for (int it = 0; it < nkt; ++it) {
-            // tile `it` has landed once at most the younger tiles' DMAs (issued after it) are outstanding
-            const int younger = min(NB - 2, nkt - 1 - it);
-            if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * LPT) : "memory");
-            else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPT) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();          // every wave's part of tile `it` is in LDS; every wave is done reading tile it-1
-            if (it + NB - 1 < nkt) {
-                int nbuf = buf + NB - 1;
-                if (nbuf >= NB) nbuf -= NB;
-                dma_tile(kt_begin + it + NB - 1, nbuf);          // into the buffer tile it-1 used
-            }
-            compute_tile(lds[buf], lds[buf] + BM * ROWB);
-            if (++buf == NB) buf = 0;
+    for (int sidx = 0; sidx < NB - 1; ++sidx)
+        if (sidx < nkt) dma_tile(kt_begin + sidx, sidx);
+    int buf = 0;
+    for (int it = 0; it < nkt; ++it) {
+        // tile `it` has landed once at most the younger tiles' DMAs (issued after it) are outstanding
+        const int younger = min(NB - 2, nkt - 1 - it);
+        if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * LPT) : "memory");
+        else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPT) : "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();              // every wave's part of tile `it` is in LDS; every wave is done reading tile it-1
+        if (it + NB - 1 < nkt) {
+            int nbuf = buf + NB - 1;
+            if (nbuf >= NB) nbuf -= NB;
+            dma_tile(kt_begin + it + NB - 1, nbuf);              // into the buffer tile it-1 used
         }
+        compute_tile(lds[buf], lds[buf] + BM * ROWB);
+        if (++buf == NB) buf = 0;
     }
 
     // ---- epilogue ----
@@ -426,33 +395,18 @@ static int check_geom(const char* op, const ConvGeom& g) {
     return RG_OK;
 }
 
-// RG_F8_BM=64|128 pins the tile height of the forward / data-gradient GEMMs (A/B measurements); anything else is ignored
-static int f8_bm_override() {
-    static const int v = rg::env_int("RG_F8_BM", 0);
-    return (v == 64 || v == 128) ? v : 0;
-}
-
-// RG_F8_NB=2 selects the register-staged two-buffer loop (the first version; kept for A/B measurements), default the 4-deep DMA ring
-static int f8_ring() {
-    static const int nb = rg::env_int("RG_F8_NB", 4);
-    return nb == 2 ? 2 : 4;
-}
-
 // fa / fb: formats of the A / B operand (0 e4m3, 1 e5m2; e5m2 x e5m2 is not instantiated)
-template <int MODE, int BM, int NB>
+template <int MODE, int BM>
 static void launch_f8_formats(dim3 grid, hipStream_t stream, const F8P& p, int fa, int fb) {
-    if (fa == 0 && fb == 0) hipLaunchKernelGGL((conv_f8_kernel<MODE, BM, 0, 0, NB>), grid, dim3(NT), 0, stream, p);
-    else if (fa == 0) hipLaunchKernelGGL((conv_f8_kernel<MODE, BM, 0, 1, NB>), grid, dim3(NT), 0, stream, p);
-    else hipLaunchKernelGGL((conv_f8_kernel<MODE, BM, 1, 0, NB>), grid, dim3(NT), 0, stream, p);
+    if (fa == 0 && fb == 0) hipLaunchKernelGGL((conv_f8_kernel<MODE, BM, 0, 0>), grid, dim3(NT), 0, stream, p);
+    else if (fa == 0) hipLaunchKernelGGL((conv_f8_kernel<MODE, BM, 0, 1>), grid, dim3(NT), 0, stream, p);
+    else hipLaunchKernelGGL((conv_f8_kernel<MODE, BM, 1, 0>), grid, dim3(NT), 0, stream, p);
 }
 
 template <int MODE>
 static void launch_f8(dim3 grid, hipStream_t stream, const F8P& p, int bm, int fa, int fb) {
-    const bool ring = f8_ring() != 2;
-    if (bm == 128 && ring) launch_f8_formats<MODE, 128, 4>(grid, stream, p, fa, fb);
-    else if (bm == 128) launch_f8_formats<MODE, 128, 2>(grid, stream, p, fa, fb);
-    else if (ring) launch_f8_formats<MODE, 64, 4>(grid, stream, p, fa, fb);
-    else launch_f8_formats<MODE, 64, 2>(grid, stream, p, fa, fb);
+    if (bm == 128) launch_f8_formats<MODE, 128>(grid, stream, p, fa, fb);
+    else launch_f8_formats<MODE, 64>(grid, stream, p, fa, fb);
 }
 
 }  // namespace
@@ -480,8 +434,7 @@ extern "C" int rg_conv2d_f8_fwd(const void* xq, const void* wq, const float* sx,
     p.Cq = Cp / 16;
     p.Kc = KH * KW * p.Cq;
     p.d_cq = make_fastdiv(p.Cq);
-    static const int bm_env = f8_bm_override();
-    const int bm = bm_env ? bm_env : (K <= 64 ? 64 : 128), fa = 0, fb = fmt_x;
+    const int bm = K <= 64 ? 64 : 128, fa = 0, fb = fmt_x;
     p.m_tiles = rg::cdiv(K, bm);
     p.n_tiles = rg::cdiv(p.Ng, BN);
     rg::ProfScope prof(rg::FAM_CONV_F8, stream, 2.0 * K * (double)p.Ng * C * KH * KW,
@@ -513,8 +466,7 @@ extern "C" int rg_conv2d_f8_dgrad(const void* dyq, const void* wq_t, const float
     p.M = C;
     p.Cq = Kp / 16;
     p.d_cq = make_fastdiv(p.Cq);
-    static const int bm_env = f8_bm_override();
-    const int bm = bm_env ? bm_env : (C <= 64 ? 64 : 128), fa = 0, fb = fmt_dy;
+    const int bm = C <= 64 ? 64 : 128, fa = 0, fb = fmt_dy;
     p.m_tiles = rg::cdiv(C, bm);
     int nt_max = 0;
     double flops = 0.0;

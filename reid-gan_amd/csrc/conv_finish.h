@@ -61,7 +61,7 @@ static unsigned* splitk_arrivals(hipStream_t stream, int tiles, const float* par
 
 static void launch_finish(hipStream_t stream, const float* partial, float* out, int M, int Ng, int PIX, const FastDiv& d_pix,
                           int splits, const Epilogue& ep) {
-    if (rg::conv::switches().splitk_vec && finish_vec_ok(partial, out, M, Ng, PIX, ep)) {      // RG_SPLITK_VEC=0: the scalar kernel
+    if (finish_vec_ok(partial, out, M, Ng, PIX, ep)) {
         hipLaunchKernelGGL(conv_splitk_finish_vec_kernel, dim3(finish_grid((int64_t)M * (Ng >> 2))), dim3(256), 0, stream, partial, out,
                            M, Ng, PIX, d_pix, make_fastdiv(Ng >> 2), splits, ep);
         return;

@@ -377,10 +377,10 @@ extern "C" int rg_conv2d_fwd(const float* x, const float* w, const float* w_krsc
         if (workspace && (size_t)slices * (size_t)K * (size_t)p.Ng * sizeof(float) <= workspace_bytes) return fwd_thin(c, per, slices);
     }
     // 3x3 / stride 1 / pad 1 layers: the tap-reuse kernel or the generic implicit GEMM on the (r,s)-major filters — whichever is
-    // faster for the geometry, measured once like the kernel implementations (RG_CONV_TUNE_PATH=0: always the tap-reuse kernel)
+    // faster for the geometry, measured once like the kernel implementations (RG_CONV_TUNE=0: always the tap-reuse kernel)
     if (fwd_halo_geom(g) && fwd_halo_operands(x, w_krsc)) {
         const HaloPlan hpl = halo_plan(p.M, p.Ng, C, &c.ws);
-        if (!path_tune_enabled()) return fwd_halo(c, hpl);
+        if (!tune_enabled()) return fwd_halo(c, hpl);
         return choose_status(tune_key(16, g, 0, 0, 0, ep_bits(p.ep, false)), stream, 2,
                              [&](int i) { return i ? fwd_generic(c) : fwd_halo(c, hpl); });
     }

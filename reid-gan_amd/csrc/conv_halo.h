@@ -149,25 +149,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(BM == 128 ? 
             const int r = (t * 11) >> 5;                       // t / 3 for t < 9
             const int toff = (r - 1) * Wh + (t - 3 * r - 1);
             const float* hsb = Hs[hb];
-#if RG_MATH == 3
             mma_kstep<T::TM, T::TN>([&](int i, int q) { return As[ab][8 * kh + q][wm * T::WTM + i * 32 + l32]; },
                                     [&](int j, int q) { return hsb[(8 * kh + q) * HP + pos[j] + toff]; }, acc);
-#else
-#pragma unroll
-            for (int ks = 0; ks < BK / 2; ++ks) {
-                const int k = 2 * ks + kh;
-                float a[T::TM], b[T::TN];
-#pragma unroll
-                for (int i = 0; i < T::TM; ++i) a[i] = As[ab][k][wm * T::WTM + i * 32 + l32];
-#pragma unroll
-                for (int j = 0; j < T::TN; ++j) b[j] = hsb[k * HP + pos[j] + toff];
-#pragma unroll
-                for (int i = 0; i < T::TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < T::TN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
-            }
-#endif
             if (!last) store_a(ab ^ 1);
             if (t == 8 && more_cb) store_h(hb ^ 1);
             __syncthreads();
@@ -179,10 +162,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(BM == 128 ? 
 }
 
 // ---- geometry test, plan, launch ----
-// H x W maps a 128-pixel tile covers with whole rows of one image or whole small images, with RG_CONV_HALO on (the layer-shape part
+// H x W maps a 128-pixel tile covers with whole rows of one image or whole small images (the layer-shape part
 // of the eligibility is the family's: fwd_halo_geom / dgrad_halo_geom)
 static bool halo_geom(int H, int W, int* HP, int* Wh, int* slab) {
-    if (!rg::conv::switches().halo || W < 4 || W > 64 || (W & (W - 1))) return false;
+    if (W < 4 || W > 64 || (W & (W - 1))) return false;
     const int R = 128 / W;                      // rows of a 128-pixel tile
     int rows, imgs;
     if (R <= H) {
@@ -214,7 +197,7 @@ static HaloPlan halo_plan(int M, int64_t Ng, int Cred, const rg::conv::Workspace
     pl.n_tiles = (int)rg::cdiv64(Ng, 128);
     const int cblocks = Cred / BK;
     const int64_t tiles = (int64_t)pl.m_tiles * pl.n_tiles;
-    const int target = rg::conv::switches().halo_wg;
+    const int target = 512;
     int64_t want = tiles >= (3 * target) / 4 ? 1 : rg::cdiv64(target, tiles);       // ~2 workgroups per CU
     if (want > cblocks / 2) want = cblocks / 2;                     // >= 2 channel blocks (18 k-tiles) per split
     if (want > 16) want = 16;

@@ -1,7 +1,6 @@
 // Implicit-GEMM 2-D convolution for gfx950 (MI355X): forward, data-gradient and weight-gradient, fp32 tensors.
-// Arithmetic (RG_MATH 3, the default): every fp32 operand is split exactly into three bf16 pieces and each product is evaluated as
-// six v_mfma_f32_32x32x16_bf16 partial products with fp32 accumulation (see "matrix arithmetic of one 16-deep k-tile" in conv_core.h);
-// RG_MATH 1 builds the round-1/2 arithmetic on v_mfma_f32_32x32x2_f32 (a k-ordered fp32 fma chain).
+// Arithmetic: every fp32 operand is split exactly into three bf16 pieces and each product is evaluated as six
+// v_mfma_f32_32x32x16_bf16 partial products with fp32 accumulation (see "matrix arithmetic of one 16-deep k-tile" in conv_core.h).
 //
 // Replaces what cuDNN/ATen do for the reference's nn.Conv2d / nn.ConvTranspose2d layers:
 //   ResNet-50 trunk           CC/clustercontrast/models/resnet_ibn_a.py:70-159 (layout pin), FD/reid/models/resnet.py:65-75
@@ -30,7 +29,7 @@
 // next tile's global loads are issued before the current tile's MFMAs.  The flat tile id is
 // remapped so that every XCD (private 4 MiB L2) works on a contiguous range of pixel tiles.
 //
-// This unit is the library's host side (conv_plan.h): the switches, the tile / split-K cost model and its candidate lists, the
+// This unit is the library's host side (conv_plan.h): the tune switch, the tile / split-K cost model and its candidate lists, the
 // measured choice with its file cache, the test knobs and the split-K arrival registry.  The kernels and the entry points that launch
 // them are in conv_fwd.hip, conv_dgrad.hip and conv_wgrad.hip, on the shared device code of conv_core.h (arithmetic, loaders,
 // epilogues), conv_halo.h (tap-reuse 3x3), conv_finish.h (split-K finishers), conv_thin.h and conv_planes.h (bf16-plane kernels).
@@ -48,16 +47,9 @@
 namespace rg {
 namespace conv {
 
-const Switches& switches() {
-    static const Switches s = {
-        env_int("RG_CONV_TUNE", 1),     env_int("RG_CONV_TUNE_PLAN", 1), env_int("RG_CONV_TUNE_PATH", 1), env_int("RG_CONV_TUNE8", 1),
-        env_int("RG_CONV_HALO", 1),     env_int("RG_HALO_WG", 512),
-        env_int("RG_THIN_CONV", 1),     env_int("RG_THIN_PX4", 1),       env_int("RG_SMALLC_PX", 1),      env_int("RG_CONV_DMA", 1),
-        env_int("RG_SPLITK_VEC", 1),    env_int("RG_DGRAD_STRIDED_SPLIT", 1),
-        env_int("RG_WGRAD_WG", 1024),   env_int("RG_WGRAD_XCD", 1),      env_int("RG_WGRAD_RSC", 0),      env_int("RG_WGRAD_SHIFT", 1),
-        env_int("RG_WGRAD_FOLD_FUSED", 1), getenv("RG_WGRAD_WG") != nullptr,
-    };
-    return s;
+bool tune_enabled() {
+    static const bool on = env_int("RG_CONV_TUNE", 1) != 0;
+    return on;
 }
 
 int validate(const char* op, const ConvGeom& g) {
@@ -149,13 +141,12 @@ Plan plan_gemm(int M, int64_t Ng, int64_t Kg, bool allow_split) {
 // one split step on about a third of the ResNet geometries (tools/sweep_tiles.py, round 4: forward -6 %, data gradient -4 % with the
 // best forced plan per layer).  So the PLAN is a measured choice too: the model's plan first, then every other tile of the shape
 // class with 1 / 2 / 3 / 4 / 6 / 8 splits that keeps >= 4 k-tiles per split and <= 1 536 workgroups; an alternative has to beat the
-// model's plan by 3 % (choose_impl).  RG_CONV_TUNE_PLAN=0 / RG_CONV_TUNE=0 / a forced plan / a GEMM under 1 GFLOP: the model's plan only.
+// model's plan by 3 % (choose_impl).  RG_CONV_TUNE=0 / a forced plan / a GEMM under 1 GFLOP: the model's plan only.
 static const double kPlanTuneMinFlop = 1.0e9;      // below 1 GFLOP a launch takes ~10 us whatever the plan: not worth ~100 timed launches
-static bool plan_tune_enabled() { return switches().tune && switches().tune_plan; }
 int plan_candidates(int M, int64_t Ng, int64_t Kg, Plan* out, int max_out) {
     out[0] = plan_gemm(M, Ng, Kg, true);
     int n = 1;
-    if (g_force_tile >= 0 || g_force_splits >= 1 || !plan_tune_enabled() || M <= 32) return n;
+    if (g_force_tile >= 0 || g_force_splits >= 1 || !tune_enabled() || M <= 32) return n;
     if (2.0 * M * (double)Ng * (double)Kg < kPlanTuneMinFlop) return n;      // launch-bound sizes: nothing to choose between
     const int64_t nk = rg::cdiv64(Kg > 0 ? Kg : 1, BK);
     int tiles[3], nt = 0;
@@ -199,12 +190,12 @@ static Plan plan_wgrad(int M, int Ng, int64_t Kg) {
     // 1024 workgroups = one full round at the kernel's 4 workgroups per CU (measured: 512 / 768 / 896 / 1024 / 1152 / 1280 /
     // 1536 -> 71.9 / 75.2 / 75.7 / 78.5 / 75.3 / 77.7 / 76.9 TFLOP/s over the FD-GAN step's wgrad launches; the fwd cost
     // model over-splits here)
-    int64_t want = rg::cdiv64(switches().wgrad_wg, mn);
+    int64_t want = rg::cdiv64(1024, mn);
     if (want > nk / 16) want = nk / 16;   // >= 16 k-tiles per split keeps partial traffic small
     if (want < 1) want = 1;
     if (want > 512) want = 512;
     while (want > 1 && want * (int64_t)M * Ng * 4 >= (1ll << 31)) --want;
-    if (switches().wgrad_xcd && want >= 8) {
+    if (want >= 8) {
         // a multiple of 8 splits (see the kernel's split -> XCD mapping); trailing splits may be empty (they store zeros)
         int64_t w8 = (want + 4) / 8 * 8;
         while (w8 > 8 && w8 * (int64_t)M * Ng * 4 >= (1ll << 31)) w8 -= 8;
@@ -225,7 +216,7 @@ static Plan plan_wgrad(int M, int Ng, int64_t Kg) {
 int wgrad_plan_candidates(int M, int Ng, int64_t Kg, Plan* out, int max_out) {
     out[0] = plan_wgrad(M, Ng, Kg);
     int n = 1;
-    if (!plan_tune_enabled() || switches().wgrad_wg_set) return n;
+    if (!tune_enabled()) return n;
     if (2.0 * M * (double)Ng * (double)Kg < kPlanTuneMinFlop) return n;
     const int64_t nk = rg::cdiv64(Kg, BK);
     const int base = out[0].splits;
@@ -286,12 +277,9 @@ unsigned* splitk_arrivals(hipStream_t stream, int tiles) {
 // one timed launch each, HIP events on the launch stream), keeps the faster (the plane path has to win by 3 %) and re-runs it if
 // it was not the last one, so the output of every call — the first included — comes from the kernel that serves the geometry
 // from then on: run-to-run bit-identity inside a process is untouched.  RG_CONV_TUNE=0: always the round-3 kernels.
-// RG_CONV_PL / rg_conv_set_planes(mask): force the plane path per family (1 forward, 2 data gradient, 4 weight gradient).
-static int& planes_mask() {
-    static int mask = env_int("RG_CONV_PL", 0);
-    return mask;
-}
-static bool planes_enabled(int family_bit) { return (planes_mask() & family_bit) != 0; }
+// rg_conv_set_planes(mask): force the plane path per family (1 forward, 2 data gradient, 4 weight gradient).
+static int g_planes_mask = 0;
+static bool planes_enabled(int family_bit) { return (g_planes_mask & family_bit) != 0; }
 static std::map<TuneKey, int> g_tune;
 static std::mutex g_tune_mu;
 // RG_CONV_TUNE_CACHE=<file>: measured choices are appended to the file (one line of 17 integers per geometry) and loaded from it by
@@ -349,8 +337,7 @@ static int choose_impl_measured(int family_bit, const TuneKey& key, hipStream_t 
     if (planes_enabled(family_bit)) {
         return run((planes_enabled(8) && ncand > 2) ? 2 : 1);
     }
-    if (!switches().tune) return run(0);
-    if (!switches().tune8 && ncand == 3 && family_bit != 0) ncand = 2;      // RG_CONV_TUNE8=0: the eight-wave form is not a candidate
+    if (!tune_enabled()) return run(0);
     {                                 // the lock covers the table only, never a launch: measurements may nest (path choice below)
         std::unique_lock<std::mutex> lock(g_tune_mu);
         tune_cache_load_locked();
@@ -431,8 +418,8 @@ extern "C" int rg_conv_set_force(int tile, int splits) {
 // development knob (tests, tools/bench_conv.py): kernel families on the bf16-plane operand path (bit 0 fwd, 1 dgrad, 2 wgrad);
 // returns the previous mask
 extern "C" int rg_conv_set_planes(int mask) {
-    const int old = planes_mask();
-    planes_mask() = mask & 15;
+    const int old = g_planes_mask;
+    g_planes_mask = mask & 15;
     return old;
 }
 

@@ -1,5 +1,5 @@
 // Host side of the fp32 convolution library that the family units (conv_fwd.hip, conv_dgrad.hip, conv_wgrad.hip) share: the
-// geometry of a call (conv_f8.hip uses it too), the tile / split-K plan, the switches and the measured choice.  Everything declared
+// geometry of a call (conv_f8.hip uses it too), the tile / split-K plan, the tune switch and the measured choice.  Everything declared
 // here is defined ONCE, in conv_igemm.hip, which also owns the state behind it (the choice table and its file, the pick knob, the
 // forced plan / plane mask, the split-K arrival registry).  No device code: the planner compiles without a kernel.
 #pragma once
@@ -55,17 +55,9 @@ inline bool aligned16(const P*... p) {
     return ((... | reinterpret_cast<uintptr_t>(p)) & 15) == 0;
 }
 
-// Switches (README "Environment switches"), each read from the environment once per process.
-struct Switches {
-    int tune, tune_plan, tune_path, tune8;          // RG_CONV_TUNE, RG_CONV_TUNE_PLAN, RG_CONV_TUNE_PATH, RG_CONV_TUNE8
-    int halo, halo_wg;                              // RG_CONV_HALO, RG_HALO_WG
-    int thin, thin_px4, smallc_px, dma;             // RG_THIN_CONV, RG_THIN_PX4, RG_SMALLC_PX, RG_CONV_DMA
-    int splitk_vec, strided_split;                  // RG_SPLITK_VEC, RG_DGRAD_STRIDED_SPLIT
-    int wgrad_wg, wgrad_xcd, wgrad_rsc, wgrad_shift, fold_fused;      // RG_WGRAD_WG / _XCD / _RSC / _SHIFT / _FOLD_FUSED
-    bool wgrad_wg_set;
-};
-const Switches& switches();
-inline bool path_tune_enabled() { return switches().tune && switches().tune_path; }     // tap-reuse against generic, measured
+// RG_CONV_TUNE (README "Environment switches", read once per process): kernel implementation, tap-reuse against generic path and
+// tile / split plan are measured choices; 0: the round-3 kernels, the tap-reuse kernel and the cost model's plan
+bool tune_enabled();
 
 // Tile (index into kTileBM / kTileBN) and split-K depth of one GEMM launch: forward, data gradient and weight gradient.
 struct Plan {

@@ -61,9 +61,6 @@ __device__ __forceinline__ float4 bload4(rsrc_t r, unsigned off) {
     const f4v v = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
     return make_float4(v.x, v.y, v.z, v.w);
 }
-__device__ __forceinline__ int4v bload16(rsrc_t r, unsigned off) {      // 16 bytes as they are (fp8 operand chunks)
-    return __builtin_bit_cast(int4v, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
-}
 __device__ __forceinline__ void bstore(rsrc_t r, unsigned off, float v) {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), r, off, 0, 0);
 }

@@ -21,9 +21,9 @@ struct ThinP {
     FastDiv d_pq, d_q;
 };
 
-// layers with <= 4 output channels: filter sizes with an instantiation (RG_THIN_CONV=0: the generic kernels)
+// layers with <= 4 output channels: filter sizes with an instantiation
 static bool thin_filter(const ConvGeom& g) {
-    return rg::conv::switches().thin && g.K >= 1 && g.K <= 4 && ((g.KH == 4 && g.KW == 4 && g.K == 1) || (g.KH == 3 && g.KW == 3));
+    return g.K >= 1 && g.K <= 4 && ((g.KH == 4 && g.KW == 4 && g.K == 1) || (g.KH == 3 && g.KW == 3));
 }
 #define THIN_DISPATCH(KERNEL, g, grid, stream, t)                                                     \
     do {                                                                                              \

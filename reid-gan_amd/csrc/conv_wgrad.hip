@@ -599,7 +599,7 @@ namespace {
 
 // thin layers, four pixels per thread (conv_wgrad_k1_px4_kernel): 3x3 / stride 1 / pad <= 1 rows of float4 multiples
 static bool thin_px4(const ConvGeom& g, const float* dy) {
-    return switches().thin_px4 && g.KH == 3 && g.KW == 3 && g.SH == 1 && g.SW == 1 && g.PH <= 1 && g.PW <= 1 && (g.Q & 3) == 0 &&
+    return g.KH == 3 && g.KW == 3 && g.SH == 1 && g.SW == 1 && g.PH <= 1 && g.PW <= 1 && (g.Q & 3) == 0 &&
            g.Q + 2 - 2 * g.PW == g.W && aligned16(dy) && ((g.P * g.Q) & 3) == 0;
 }
 #define THIN_PX4_DISPATCH(KERNEL, g, grid, stream, t)                                                 \
@@ -617,8 +617,14 @@ static int thin_wgrad_per_slice(int C, int64_t Ng) {
     return (int)((rg::cdiv64(Ng, slices) + 3) / 4 * 4);      // a multiple of four pixels (conv_wgrad_k1_px4_kernel)
 }
 
+// RG_WGRAD_RSC=1 (README "Environment switches", read once per process): (r,s)-major columns where the geometry allows
+static bool wgrad_rsc_enabled() {
+    static const bool on = rg::env_int("RG_WGRAD_RSC", 0) != 0;
+    return on;
+}
+
 static void launch_reduce(hipStream_t stream, const float* ws, float* out, int64_t n, int splits, int rsc, int C, int RS) {
-    if (switches().splitk_vec && aligned16(ws, out) && (n & 3) == 0)           // RG_SPLITK_VEC=0: the scalar kernel
+    if (aligned16(ws, out) && (n & 3) == 0)
         hipLaunchKernelGGL(splitk_reduce_vec_kernel, dim3((unsigned)rg::cdiv64(n >> 2, 64)), dim3(256), 0, stream, ws, out, n, splits, rsc,
                            C, RS);
     else
@@ -680,7 +686,7 @@ static int wgrad_run_plan(const WgradCall& c, const Plan& pl) {
     }
     RG_REQUIRE(need < (1ull << 31), "rg_conv2d_wgrad: partial buffer exceeds 2 GiB");
     // (r,s)-major columns (RG_WGRAD_RSC=1): always through the workspace (the finishing kernel restores the checkpoint order)
-    const bool rsc = switches().wgrad_rsc && (g.KH * g.KW > 1) && (g.C % 16 == 0);
+    const bool rsc = wgrad_rsc_enabled() && (g.KH * g.KW > 1) && (g.C % 16 == 0);
     const bool via_ws = pl.splits > 1 || rsc;
     float* const partial = static_cast<float*>(c.ws.ptr);
     p.a_vec4 = rsc ? 1 : 0;
@@ -693,9 +699,9 @@ static int wgrad_run_plan(const WgradCall& c, const Plan& pl) {
         rg::ProfScope prof(rg::FAM_CONV_WGRAD, stream, 2.0 * p.M * (double)p.Ng * p.Kg, alg_bytes(g));
         const bool veca = aligned16(c.o.x, c.o.dy) && ((g.P * g.Q) % 4 == 0);
         bool vec = veca && g.KH == 1 && g.KW == 1 && g.SH == 1 && g.SW == 1 && g.PH == 0 && g.PW == 0;
-        if (!vec && !rsc && switches().wgrad_shift && veca && g.SH == 1 && g.SW == 1 && g.PW <= 1 && g.KW <= g.PW + 2 && g.Q % 4 == 0 &&
+        if (!vec && !rsc && veca && g.SH == 1 && g.SW == 1 && g.PW <= 1 && g.KW <= g.PW + 2 && g.Q % 4 == 0 &&
             g.W >= 4 && g.KW * g.KH > 1) {
-            vec = true;                  // im2col operand = shifted float4 loads of x (conv_wgrad_kernel, p.wshift; RG_WGRAD_SHIFT=0: never)
+            vec = true;                  // im2col operand = shifted float4 loads of x (conv_wgrad_kernel, p.wshift)
             p.wshift = 1;
         }
         const TuneKey tk = tune_key(4, g, (vec ? 2 : 0) + (veca ? 1 : 0) + p.wshift * 4, pl.tile, pl.splits, 0);
@@ -707,8 +713,8 @@ static int wgrad_run_plan(const WgradCall& c, const Plan& pl) {
         if (int e = rg::check_launch("rg_conv2d_wgrad")) return e;
         if (via_ws) {
             const int64_t n = (int64_t)p.M * p.Ng;
-            if (fold && !rsc && (p.Ng & 3) == 0 && aligned16(partial, dw, fold->w) && switches().fold_fused) {
-                // reduction + BatchNorm-fold finish in one launch (one workgroup per filter; RG_WGRAD_FOLD_FUSED=0: two launches)
+            if (fold && !rsc && (p.Ng & 3) == 0 && aligned16(partial, dw, fold->w)) {
+                // reduction + BatchNorm-fold finish in one launch (one workgroup per filter)
                 hipLaunchKernelGGL(splitk_reduce_fold_kernel, dim3(p.M), dim3(256), 0, stream, partial, dw, fold->w, p.Ng, n, pl.splits,
                                    fold->scale, fold->invstd, fold->mean, fold->sum_g, fold->partials, fold->n_slices, fold->dbeta,
                                    fold->dgamma);

@@ -84,8 +84,7 @@ class _capture_mode(object):
 
     def __enter__(self):
         self.side = ops._SIDE["on"]
-        if not ops._GRAPH_SIDE:
-            ops._SIDE["on"] = False
+        ops._SIDE["on"] = False
         ops.CAPTURING[0] += 1
         ops.CAPTURE_GEN[0] += 1
 

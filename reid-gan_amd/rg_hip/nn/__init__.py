@@ -38,5 +38,5 @@ from .conv import _KrscCache
 
 # ---- the other module-level underscore names of the former single file: nothing outside reads them today, they stay reachable ----
 from ._base import _pair, _geom_gflop, _bias_grad
-from .conv import _f8_backward_operands, _KRSC_GROUPS
+from .conv import _f8_backward_operands
 from .fold import _Fold, _foldable, _fold_key, _FOLD_IN_CAPTURE

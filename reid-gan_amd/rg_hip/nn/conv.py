@@ -3,7 +3,6 @@ convolutions: per layer (_KrscCache) or one launch per network and optimizer ste
 from __future__ import absolute_import
 
 import math
-import os
 
 import torch
 from torch import nn
@@ -110,16 +109,11 @@ class KrscGroup(object):
         return m._wk
 
 
-_KRSC_GROUPS = os.environ.get("RG_KRSC_GROUP", "1") != "0"      # A/B switch: 0 = one re-layout launch per filter
-
-
 def group_krsc(net):
     """give the plain convolutions of `net` one shared KrscGroup (idempotent; called on a network's first run)"""
     if net.__dict__.get("_krsc_grouped"):
         return
     net.__dict__["_krsc_grouped"] = True
-    if not _KRSC_GROUPS:
-        return
     root = net if isinstance(net, nn.Module) else getattr(net, "net", None)     # tape programs over another module's layers
     if not isinstance(root, nn.Module):
         return

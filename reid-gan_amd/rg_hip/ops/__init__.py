@@ -75,15 +75,14 @@ from .databank import bank_lut, BankDraws, bank_draws, bank_reid_batch, bank_gan
 
 # ---- underscore names that code outside the package reads (rg_hip.nn / netgraph / parallel / lowp, the tests, tools/) ------------
 from ._base import _stream, _p, _chk, _pair, _ws_query, _ws_sizes
-from .streams import _side_session, _SIDE, _GRAPH_SIDE
+from .streams import _side_session, _SIDE
 from .gan import _SNDesc
 from .profile import _PROFILING
 from .infomap import _infomap_leaf_units, _infomap_totals, _infomap_codelength_of
 
 # ---- the other module-level underscore names of the former single file: nothing outside reads them today, they stay reachable ------
 from ._base import _DEV, _bind_device, _dense, _chk_rr, _nchw, _same_size, _eps32, _list_total, _SPLITK_INKERNEL, _Workspace, _ws
-from .streams import _HANDED, _PROBE_US, _share_a_queue, _INLINE_SIDE, _SideSession, _SIDE_MIN_US, _GRAPH_SIDE_MIN_US
-from .norm import _BN_FUSED
+from .streams import _HANDED, _PROBE_US, _share_a_queue, _INLINE_SIDE, _SideSession, _SIDE_MIN_US
 from .eltwise import _CONST_FILL, _CLOCK
 from .loss import _loss_ws, _verif_vec
 from .retrieval import _pair_vec

@@ -2,7 +2,6 @@
 norm_dsbn.hip, norm_fold.hip."""
 from __future__ import absolute_import
 
-import os
 
 import torch
 
@@ -49,13 +48,8 @@ def bn_bwd_reduce(x, dy, y_act, mean, stat, stat_is_var=False, eps=1e-5, act=ACT
     return sum_dy, sum_dy_xhat
 
 
-_BN_FUSED = os.environ.get("RG_BN_FUSED", "1") != "0"
-
-
 def bn_train_fused_ok(x):
     """does this activation qualify for the one-launch train-mode BatchNorm kernels (small per-channel extent, many channels)?"""
-    if not _BN_FUSED:
-        return False
     N, C, HW = _nchw(x)
     return bool(_ws_query("rg_bn_train_fused_ok", N, C, HW))
 

@@ -33,9 +33,6 @@ def _share_a_queue(a, b):
         b.synchronize()
         dt = 1e6 * (time.perf_counter() - t0)
         best = dt if best is None else min(best, dt)
-    if os.environ.get("RG_STREAM_PROBE_DEBUG") == "1":
-        import sys
-        sys.stderr.write("[stream probe] %#x vs %#x: %.0f us\n" % (a.cuda_stream, b.cuda_stream, best))
     return best > 1.6 * _PROBE_US
 
 
@@ -138,18 +135,12 @@ def side_join():
 # Moving a launch to the side stream costs the host ~60 us (event record / wait, stream switch: profiles/r03_host_cost.txt shows
 # 3.0 ms per step for the 48 side launches of the DPTN step, whose kernels take 5-20 us each): only work that runs long enough for
 # the overlap to buy something goes there.  Estimated from the algorithmic FLOPs at the rates the kernel families reach.
-_SIDE_MIN_US = float(os.environ.get("RG_SIDE_MIN_US", "25"))
-
-
-_GRAPH_SIDE = os.environ.get("RG_GRAPH_SIDE", "0") == "1"          # captured backward programs keep the side stream (fork / join nodes)
-_GRAPH_SIDE_MIN_US = float(os.environ.get("RG_GRAPH_SIDE_MIN_US", "4"))
+# (Captured network programs run on one stream: rg_hip.netgraph switches the side stream off while it captures.)
+_SIDE_MIN_US = 25.0
 
 
 def side_worth(gflop, fp8=False):
-    us = gflop / (0.30 if fp8 else 0.08)
-    if CAPTURING[0]:
-        return us >= _GRAPH_SIDE_MIN_US      # the hand-off is recorded once: only the GPU-side concurrency counts
-    return us >= _SIDE_MIN_US
+    return gflop / (0.30 if fp8 else 0.08) >= _SIDE_MIN_US
 
 
 def side_call(fn, *operands, worth=True):

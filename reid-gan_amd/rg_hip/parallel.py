@@ -35,13 +35,8 @@ def init_process_group(rank, world, local_rank, **kw):
     (main, weight-gradient side stream, FD-GAN's auxiliary stream and its side stream); a FIFTH active hardware queue — a
     high-priority collective stream, or GPU_MAX_HW_QUEUES=8 — makes the queue scheduler time-slice them and every cross-stream
     dependency then waits for a slice: measured on one rank, config 2, 35.4 -> 46.9 ms (high-priority stream) and 56-66 ms
-    (8 queues) per step (`tools/debug/rccl_ab.sh`, `profiles/r04_hw_queues.txt`).  RG_NCCL_HIGH_PRIO=1 asks for the high-priority
-    stream anyway (A/B)."""
-    opts = None
-    if os.environ.get("RG_NCCL_HIGH_PRIO", "0") == "1":
-        opts = dist.ProcessGroupNCCL.Options(is_high_priority_stream=True)
-    return dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank),
-                                   pg_options=opts, **kw)
+    (8 queues) per step (`profiles/r04_hw_queues.txt`)."""
+    return dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank), **kw)
 
 
 def world_size():
@@ -232,8 +227,6 @@ def attach_stage_hooks(reducer, *modules):
     from .nn import Sequential
     from .resnet_trunk import TVResNet
     n = 0
-    if os.environ.get("RG_STAGE_BUCKETS", "1") == "0":       # A/B switch: one reduction per arena after the backward pass (round 3)
-        return 0
     for root in modules:
         root = getattr(root, "module", root)
         for m in root.modules():

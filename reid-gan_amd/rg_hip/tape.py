@@ -79,7 +79,7 @@ def run_backward(net, tape, dys, need, params):
     """Run the backward program of `net` and settle the parameter gradients: a gradient written straight into the optimizer's
     arena is assigned to `.grad`, a later contribution is accumulated into it, everything else is handed to autograd.
     -> (dxs padded to len(need), gradient per parameter for autograd (None when settled here), [(param, arena view)] assigned)"""
-    ops.side_begin()                  # (inside a capture: a no-op unless RG_GRAPH_SIDE keeps the weight-gradient side stream on)
+    ops.side_begin()                  # (inside a capture: a no-op, the side stream is off)
     try:
         dxs = net.tb(tape, *dys, need_dx=any(need))
     finally:
@@ -130,17 +130,11 @@ class _NetFn(torch.autograd.Function):
         return (None, None) + tuple(d if n else None for d, n in zip(dxs, need)) + tuple(grads)
 
 
-_AUTOGRAD_MT = __import__("os").environ.get("RG_AUTOGRAD_MT") == "1"      # A/B switch: leave the engine's worker thread on
-
-
 def backward(loss, **kw):
     """loss.backward() with the network backward programs run on the CALLING thread: the autograd engine otherwise hands every
     node to its per-device worker thread, and the hand-off (plus the GIL ping-pong between the two threads while one of them
     enqueues kernels) costs ~1 ms per step on the small-kernel steps (tools/debug/host_cost.py: DPTN step 15.7 -> 14.8 ms).
     Streams behave as before: the engine restores each node's forward stream either way."""
-    if _AUTOGRAD_MT:
-        loss.backward(**kw)
-        return
     with torch.autograd.set_multithreading_enabled(False):
         loss.backward(**kw)
 
