@@ -819,6 +819,27 @@ int rg_bank_gan_batch(const unsigned char* bank_u8, int M, int Hg, int Wg, const
  * when the bank is built (the reference recomputes them from a pandas row per draw). */
 int rg_bank_pose_batch(const int* centres, int M, int J, const int* idx, const int* flip, int flip_stride, float sigma, float* out,
                        int N, int Hg, int Wg, rg_stream_t stream);
+/* FD-GAN stage II's images (FD/train.py:21-44, FD/reid/utils/data/preprocessor.py:63-98: RectScale -> RandomSizedEarser ->
+ * RandomHorizontalFlip -> ToTensor -> Normalize for `origin`; RectScale -> flip -> ToTensor -> Normalize for `target`) from planes
+ * bank_u8[M][H][W][3] that hold RectScale's result.  params[N][8] int32 = (flip, 0, 0, er0, ec0, eh, ew, rgb) with
+ * rgb = R | G << 8 | B << 16; for out[n][c][y][x]:
+ *     xs = flip ? W-1-x : x                                   (the eraser runs BEFORE the flip: pre-flip coordinates)
+ *     eh > 0 and (y, xs) in [er0, er0+eh) x [ec0, ec0+ew)  -> lut[c][byte c of rgb]    (the patch is pasted on BYTES, before
+ *                                                             ToTensor / Normalize, so it goes through the same table)
+ *     otherwise                                            -> lut[c][bank_u8[idx[n]][y][xs][c]]
+ * This is rg_bank_reid_batch's kernel with one more compile-time case: no floating-point arithmetic, 16-byte stores where
+ * W % 4 == 0.  A target row is a row with eh = 0, so ONE launch writes origin and target of both items of every pair. */
+int rg_bank_fd_image_batch(const unsigned char* bank_u8, int M, int H, int W, const int* idx, const int* params, const float* lut,
+                           float* out, int N, rg_stream_t stream);
+/* FD-GAN stage II's pose maps (preprocessor.py:84-91, 114-131): out[N][J][H][W] = rg_pose_maps mode 0 of the landmarks
+ * landmarks[idx[n]][J][2] = (row, col) as `_load_landmark` gives them (computed once per image), with the sample's own draws
+ * pose_params[N][4] int32 = (flip, sigma, erased joint or -1, 0), read at (y, flip ? W-1-x : x).  The erased joint and any
+ * coordinate outside [0, H) x [0, W) (-1: not detected) give a zero map.  Same profile code as rg_pose_maps (csrc/pose_profiles.h):
+ * bit-equal to rg_pose_maps(mode 0) on the gathered landmarks followed by the flip.  The closed form counts the first mirror
+ * image only: the caller guarantees int(4 sigma + 0.5) <= min(H, W) (rg_hip/ops/databank.py refuses anything else).  One
+ * workgroup per (sample, joint), 16-byte row stores where W % 4 == 0; N <= 65535, H, W <= 1024. */
+int rg_bank_fd_pose_batch(const int* landmarks, int M, int J, const int* idx, const int* pose_params, float* out, int N, int H,
+                          int W, rg_stream_t stream);
 
 #ifdef __cplusplus
 }

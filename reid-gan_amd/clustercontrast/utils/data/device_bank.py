@@ -74,7 +74,7 @@ def stage_centres(cords, old_sizes, gan_size):
     return np.clip(c, _SENTINEL, 2 ** 31 - 1).astype(np.int32)
 
 
-def _decode(path, reid_size, gan_size):
+def _decode(path, reid_size, gan_size, reid_resample="bicubic"):
     from PIL import Image
     img = Image.open(path).convert("RGB")
     old = (img.size[1], img.size[0])
@@ -83,7 +83,10 @@ def _decode(path, reid_size, gan_size):
     # size over the full box returns a copy, so this is what torchvision's call gives too
     bicubic = getattr(Image, "Resampling", Image).BICUBIC
     bilinear = getattr(Image, "Resampling", Image).BILINEAR
-    reid = img if (img.size[1], img.size[0]) == tuple(reid_size) else img.resize((reid_size[1], reid_size[0]), bicubic)
+    # reid_resample 'bilinear': FD-GAN's RectScale(height, width) (FD/reid/utils/data/transforms.py:9-19), the same rule with
+    # PIL's BILINEAR
+    reid = img if (img.size[1], img.size[0]) == tuple(reid_size) else \
+        img.resize((reid_size[1], reid_size[0]), bicubic if reid_resample == "bicubic" else bilinear)
     out_r = np.asarray(reid, dtype=np.uint8)
     out_g = None
     if gan_size is not None:
@@ -92,12 +95,19 @@ def _decode(path, reid_size, gan_size):
     return out_r, out_g, old
 
 
-def stage_files(entries, root=None, reid_size=(256, 128), gan_size=(128, 64), pose_file=None, workers=None):
+def stage_files(entries, root=None, reid_size=(256, 128), gan_size=(128, 64), pose_file=None, workers=None, reid_resample="bicubic",
+                pose_root=None):
     """Decode every file of `entries` = [(fname, pid, camid)] ONCE and resize it to both plane sizes on the host.  Returns the
-    keyword arguments of DeviceImageBank.from_arrays as numpy arrays / lists; nothing here touches a device."""
+    keyword arguments of DeviceImageBank.from_arrays as numpy arrays / lists; nothing here touches a device.
+
+    reid_resample: 'bicubic' (T.Resize(..., BICUBIC)) or 'bilinear' (FD-GAN's RectScale).  pose_root: the directory of FD-GAN's
+    landmark files (splitext(fname) + '.txt'); adds `landmarks`, the int32 [M, J, 2] table of `_load_landmark` at reid_size
+    (reid.utils.data.device_pairs.stage_landmarks)."""
     entries = list(entries)
     if not entries:
         raise ValueError("stage_files: no entries")
+    if reid_resample not in ("bicubic", "bilinear"):
+        raise ValueError("stage_files: reid_resample must be 'bicubic' or 'bilinear', got %r" % (reid_resample,))
     reid_size = (int(reid_size[0]), int(reid_size[1]))
     gan_size = None if gan_size is None else (int(gan_size[0]), int(gan_size[1]))
     paths = [f if root is None else osp.join(root, f) for f, _, _ in entries]
@@ -108,7 +118,7 @@ def stage_files(entries, root=None, reid_size=(256, 128), gan_size=(128, 64), po
     old = np.empty((M, 2), dtype=np.int64)
 
     def one(m):
-        r, g, o = _decode(paths[m], reid_size, gan_size)
+        r, g, o = _decode(paths[m], reid_size, gan_size, reid_resample)
         reid[m] = r
         if gan is not None:
             gan[m] = g
@@ -124,17 +134,21 @@ def stage_files(entries, root=None, reid_size=(256, 128), gan_size=(128, 64), po
     if pose_file is not None:
         table = read_pose_csv(pose_file)
         cords = np.stack([table[osp.split(p)[-1]] for p in paths])
-    return dict(reid_u8=reid, fnames=[e[0] for e in entries], pids=[int(e[1]) for e in entries],
-                camids=[int(e[2]) for e in entries], gan_u8=gan, cords=cords, old_sizes=old)
+    out = dict(reid_u8=reid, fnames=[e[0] for e in entries], pids=[int(e[1]) for e in entries],
+               camids=[int(e[2]) for e in entries], gan_u8=gan, cords=cords, old_sizes=old)
+    if pose_root is not None:
+        from reid.utils.data.device_pairs import stage_landmarks
+        out["landmarks"] = stage_landmarks([e[0] for e in entries], pose_root, old, reid_size)
+    return out
 
 
 # ---- the bank -----------------------------------------------------------------------------------------------------------------
 class DeviceImageBank(object):
     """uint8 planes of every image of a data set on the device: `reid` [M, Hs, Ws, 3], `gan` [M, Hg, Wg, 3] or None, `centres`
-    int32 [M, J, 2] or None, plus the host bookkeeping (`fnames`, `pids`, `camids`, `old_sizes`, `row`: fname -> bank row)."""
+    int32 [M, J, 2] or None, `landmarks` int32 [M, J, 2] or None (FD-GAN's `_load_landmark` at the ReID plane's size), plus the host bookkeeping (`fnames`, `pids`, `camids`, `old_sizes`, `row`: fname -> bank row)."""
 
-    def __init__(self, reid, gan, centres, fnames, pids, camids, old_sizes):
-        self.reid, self.gan, self.centres = reid, gan, centres
+    def __init__(self, reid, gan, centres, fnames, pids, camids, old_sizes, landmarks=None):
+        self.reid, self.gan, self.centres, self.landmarks = reid, gan, centres, landmarks
         self.fnames, self.pids, self.camids, self.old_sizes = list(fnames), list(pids), list(camids), old_sizes
         self.row = {f: m for m, f in enumerate(self.fnames)}
         if len(self.row) != len(self.fnames):
@@ -146,7 +160,7 @@ class DeviceImageBank(object):
 
     @property
     def nbytes(self):
-        return sum(t.numel() * t.element_size() for t in (self.reid, self.gan, self.centres) if t is not None)
+        return sum(t.numel() * t.element_size() for t in (self.reid, self.gan, self.centres, self.landmarks) if t is not None)
 
     @property
     def reid_size(self):
@@ -157,7 +171,8 @@ class DeviceImageBank(object):
         return None if self.gan is None else (self.gan.shape[1], self.gan.shape[2])
 
     @classmethod
-    def from_arrays(cls, reid_u8, fnames, pids, camids, gan_u8=None, cords=None, old_sizes=None, centres=None, device=None):
+    def from_arrays(cls, reid_u8, fnames, pids, camids, gan_u8=None, cords=None, old_sizes=None, centres=None, device=None,
+                    landmarks=None):
         """From already-resized uint8 arrays [M, H, W, 3] (numpy or torch).  `cords` [M, J, 2] = (y, x) in the ORIGINAL image's
         pixels with `old_sizes` [M, 2] = (height, width) of the originals (None: the GAN plane's size), or a ready `centres`
         table; the upload is the only device work."""
@@ -186,13 +201,20 @@ class DeviceImageBank(object):
             if centres.dtype != torch.int32 or centres.dim() != 3 or centres.shape[0] != len(fnames) or centres.shape[2] != 2:
                 raise ValueError("DeviceImageBank: centres must be int32 [M, J, 2]")
             centres = centres.contiguous().to(device)
-        return cls(reid, gan, centres, fnames, pids, camids, None if old_sizes is None else np.asarray(old_sizes))
+        if landmarks is not None:
+            landmarks = torch.as_tensor(landmarks)
+            if landmarks.dtype != torch.int32 or landmarks.dim() != 3 or landmarks.shape[0] != len(fnames) or landmarks.shape[2] != 2:
+                raise ValueError("DeviceImageBank: landmarks must be int32 [M, J, 2]")
+            landmarks = landmarks.contiguous().to(device)
+        return cls(reid, gan, centres, fnames, pids, camids, None if old_sizes is None else np.asarray(old_sizes), landmarks)
 
     @classmethod
-    def from_files(cls, entries, root=None, reid_size=(256, 128), gan_size=(128, 64), pose_file=None, workers=None, device=None):
+    def from_files(cls, entries, root=None, reid_size=(256, 128), gan_size=(128, 64), pose_file=None, workers=None, device=None,
+                   reid_resample="bicubic", pose_root=None):
         """Decode each file of the reference's (fname, pid, camid) triples once with PIL, resize it to both plane sizes on the
         host (`stage_files`) and upload."""
-        return cls.from_arrays(device=device, **stage_files(entries, root, reid_size, gan_size, pose_file, workers))
+        return cls.from_arrays(device=device, **stage_files(entries, root, reid_size, gan_size, pose_file, workers, reid_resample,
+                                                            pose_root))
 
 
 # ---- loaders ------------------------------------------------------------------------------------------------------------------

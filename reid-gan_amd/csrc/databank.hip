@@ -13,20 +13,32 @@
 // and of its neighbours come from one 3*Ws-byte row; a thread takes 4 consecutive output columns of one output row for all
 // three channels (12 neighbouring bytes in, three 16-byte stores out — the output, 12x the input, is what the kernel is
 // bound by).  Where W % 4 != 0 the rows of the output planes are not 16-byte aligned and a thread takes one column.
+//
+// FD-GAN stage II (FD/train.py:21-44, FD/reid/utils/data/preprocessor.py:63-98) draws pairs of items, each
+//   RectScale -> RandomSizedEarser (a colour patch pasted on the BYTES) -> RandomHorizontalFlip -> ToTensor -> Normalize     origin
+//   RectScale -> flip -> ToTensor -> Normalize                                                                               target
+//   _generate_pose_map of the target's landmarks (one joint erased, or sigma drawn) -> np.flip(maps, 2)                      posemap
+// RectScale again precedes every draw: rg_bank_fd_image_batch is the image gather with the patch looked up in the table by its
+// colour bytes, rg_bank_fd_pose_batch the filtered-impulse form of the maps (pose_profiles.h) from a per-image landmark table.
+#include "pose_profiles.h"
 #include "rg_common.h"
 
 namespace {
 
-constexpr int MAXDIM = 1024;      // Hg, Wg <= MAXDIM for the pose maps (profiles live in LDS, as csrc/datagen.hip)
+constexpr int MAXDIM = rg::POSE_MAXDIM;      // Hg, Wg <= MAXDIM for the pose maps (profiles live in LDS, as csrc/datagen.hip)
+enum { KIND_GAN = 0, KIND_REID = 1, KIND_FD = 2 };
 
 // One output pixel of channel c.  (y, xs): output row and PRE-FLIP output column.  `plane` is the sample's stored plane or
 // nullptr (index outside the bank: the wrapper refuses it before the launch; here it reads nothing).
-template <bool REID>
+// KIND_REID: the rectangle holds fill3[c] (RandomErasing after Normalize); KIND_FD: it holds the table entry of byte c of `rgb`
+// (RandomSizedEarser pastes bytes before ToTensor / Normalize); KIND_GAN: no rectangle.
+template <int KIND>
 __device__ __forceinline__ float bank_pixel(const unsigned char* __restrict__ plane, const float* lut, const float* fill3, int c,
                                             int y, int xs, int Hs, int Ws, int top, int left, int pad, int er0, int ec0, int eh,
-                                            int ew) {
-    if (REID) {
-        if (eh > 0 && y >= er0 && y < er0 + eh && xs >= ec0 && xs < ec0 + ew) return fill3[c];
+                                            int ew, int rgb) {
+    if (KIND != KIND_GAN) {
+        if (eh > 0 && y >= er0 && y < er0 + eh && xs >= ec0 && xs < ec0 + ew)
+            return KIND == KIND_FD ? lut[c * 256 + ((rgb >> (8 * c)) & 255)] : fill3[c];
     }
     const int r = top + y - pad, q = left + xs - pad;
     int b = 0;                                        // outside the stored plane: the padding is black BEFORE Normalize
@@ -34,9 +46,10 @@ __device__ __forceinline__ float bank_pixel(const unsigned char* __restrict__ pl
     return lut[c * 256 + b];
 }
 
-// VEC: 4 output columns per thread (W % 4 == 0), else 1.  REID: params[N][8] = (flip, top, left, er0, ec0, eh, ew, -);
-// otherwise params points at the flips with `pstride` ints between samples, and the view is the whole plane.
-template <bool REID, int VEC>
+// VEC: 4 output columns per thread (W % 4 == 0), else 1.  KIND_REID: params[N][8] = (flip, top, left, er0, ec0, eh, ew, -);
+// KIND_FD: params[N][8] = (flip, -, -, er0, ec0, eh, ew, rgb) and the view is the whole plane; KIND_GAN: params points at the
+// flips with `pstride` ints between samples, and the view is the whole plane.
+template <int KIND, int VEC>
 __global__ __launch_bounds__(256) void bank_image_kernel(const unsigned char* __restrict__ bank, int M, int Hs, int Ws,
                                                          const int* __restrict__ idx, const int* __restrict__ params, int pstride,
                                                          const float* __restrict__ lut_g, const float* __restrict__ fill,
@@ -44,7 +57,7 @@ __global__ __launch_bounds__(256) void bank_image_kernel(const unsigned char* __
     __shared__ float lut[768];
     __shared__ float fill3[3];
     for (int i = threadIdx.x; i < 768; i += 256) lut[i] = lut_g[i];
-    if (threadIdx.x < 3) fill3[threadIdx.x] = (REID && fill) ? fill[threadIdx.x] : 0.f;
+    if (threadIdx.x < 3) fill3[threadIdx.x] = (KIND == KIND_REID && fill) ? fill[threadIdx.x] : 0.f;
     __syncthreads();
     const int Wv = W / VEC;
     const int64_t plane_bytes = (int64_t)Hs * Ws * 3;
@@ -55,9 +68,12 @@ __global__ __launch_bounds__(256) void bank_image_kernel(const unsigned char* __
         const int n = (int)(t / H);
         const int* p = params + (int64_t)n * pstride;
         const int flip = p[0];
-        int top = 0, left = 0, er0 = 0, ec0 = 0, eh = 0, ew = 0;
-        if (REID) {
+        int top = 0, left = 0, er0 = 0, ec0 = 0, eh = 0, ew = 0, rgb = 0;
+        if (KIND == KIND_REID) {
             top = p[1], left = p[2], er0 = p[3], ec0 = p[4], eh = p[5], ew = p[6];
+        }
+        if (KIND == KIND_FD) {
+            er0 = p[3], ec0 = p[4], eh = p[5], ew = p[6], rgb = p[7];
         }
         const int m = idx[n];
         const unsigned char* plane = (unsigned)m < (unsigned)M ? bank + (int64_t)m * plane_bytes : nullptr;
@@ -69,18 +85,19 @@ __global__ __launch_bounds__(256) void bank_image_kernel(const unsigned char* __
                 float* vp = reinterpret_cast<float*>(&v);
                 for (int k = 0; k < 4; ++k) {
                     const int x = xv * 4 + k;
-                    vp[k] = bank_pixel<REID>(plane, lut, fill3, c, y, flip ? W - 1 - x : x, Hs, Ws, top, left, pad, er0, ec0, eh, ew);
+                    vp[k] = bank_pixel<KIND>(plane, lut, fill3, c, y, flip ? W - 1 - x : x, Hs, Ws, top, left, pad, er0, ec0, eh, ew, rgb);
                 }
                 *reinterpret_cast<float4*>(o + c * cstride) = v;
             }
         } else {
             for (int c = 0; c < 3; ++c)
-                o[c * cstride] = bank_pixel<REID>(plane, lut, fill3, c, y, flip ? W - 1 - xv : xv, Hs, Ws, top, left, pad, er0, ec0, eh, ew);
+                o[c * cstride] = bank_pixel<KIND>(plane, lut, fill3, c, y, flip ? W - 1 - xv : xv, Hs, Ws, top, left, pad, er0, ec0, eh, ew,
+                                                rgb);
         }
     }
 }
 
-template <bool REID>
+template <int KIND>
 int launch_image(const char* who, const unsigned char* bank, int M, int Hs, int Ws, const int* idx, const int* params, int pstride,
                  const float* lut, const float* fill, float* out, int N, int H, int W, int pad, hipStream_t stream) {
     const bool vec = (W % 4 == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
@@ -89,10 +106,10 @@ int launch_image(const char* who, const unsigned char* bank, int M, int Hs, int 
     if (g > 16384) g = 16384;
     rg::ProfScope prof(rg::FAM_MISC, stream, 0.0, 12.0 * N * (double)H * W + 3.0 * N * (double)H * W);
     if (vec)
-        hipLaunchKernelGGL((bank_image_kernel<REID, 4>), dim3((unsigned)g), dim3(256), 0, stream, bank, M, Hs, Ws, idx, params, pstride,
+        hipLaunchKernelGGL((bank_image_kernel<KIND, 4>), dim3((unsigned)g), dim3(256), 0, stream, bank, M, Hs, Ws, idx, params, pstride,
                            lut, fill, out, H, W, pad, items);
     else
-        hipLaunchKernelGGL((bank_image_kernel<REID, 1>), dim3((unsigned)g), dim3(256), 0, stream, bank, M, Hs, Ws, idx, params, pstride,
+        hipLaunchKernelGGL((bank_image_kernel<KIND, 1>), dim3((unsigned)g), dim3(256), 0, stream, bank, M, Hs, Ws, idx, params, pstride,
                            lut, fill, out, H, W, pad, items);
     return rg::check_launch(who);
 }
@@ -127,6 +144,55 @@ __global__ __launch_bounds__(256) void bank_pose_kernel(const int* __restrict__ 
     }
 }
 
+// grid (J, N): one workgroup per (sample, joint); the mode-0 expression of pose_maps_kernel (csrc/datagen.hip) through the shared
+// profile code of pose_profiles.h, with the sample's own sigma, read at (y, flip ? W-1-x : x).  pp[N][4] = (flip, sigma, erased
+// joint or -1, -).  VEC 4: a thread writes 4 neighbouring columns of a row with one 16-byte store (W % 4 == 0).
+template <int VEC>
+__global__ __launch_bounds__(256) void bank_fd_pose_kernel(const int* __restrict__ landmarks, int M, const int* __restrict__ idx,
+                                                           const int* __restrict__ pp, float* __restrict__ out, int J, int H, int W) {
+    __shared__ double fy[MAXDIM], fx[MAXDIM];
+    __shared__ double red[8];
+    const int j = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
+    const int m = idx[n];
+    const int flip = pp[n * 4 + 0], sigma = pp[n * 4 + 1], erased = pp[n * 4 + 2];
+    float* o = out + ((int64_t)n * J + j) * H * W;
+    int cy = -1, cx = -1;
+    if ((unsigned)m < (unsigned)M) {
+        cy = landmarks[((int64_t)m * J + j) * 2 + 0];
+        cx = landmarks[((int64_t)m * J + j) * 2 + 1];
+    }
+    const int items = H * W / VEC;
+    // erased, undetected (-1) or outside the map -> zeros (uniform per block)
+    if (j == erased || cy < 0 || cx < 0 || cy >= H || cx >= W) {
+        if (VEC == 4) {
+            for (int i = tid; i < items; i += 256) reinterpret_cast<float4*>(o)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+            for (int i = tid; i < items; i += 256) o[i] = 0.f;
+        }
+        return;
+    }
+    const double inv = rg::fd_pose_profiles(fy, fx, red, cy, cx, H, W, (double)sigma);
+    if (VEC == 4) {
+        const int Wv = W / 4;
+        for (int i = tid; i < items; i += 256) {
+            const int y = i / Wv, x0 = (i - y * Wv) * 4;
+            const double row = fy[y];
+            float4 v;
+            float* vp = reinterpret_cast<float*>(&v);
+            for (int k = 0; k < 4; ++k) {
+                const int x = x0 + k;
+                vp[k] = (float)(row * fx[flip ? W - 1 - x : x] * inv);
+            }
+            reinterpret_cast<float4*>(o)[i] = v;
+        }
+    } else {
+        for (int i = tid; i < items; i += 256) {
+            const int y = i / W, x = i - y * W;
+            o[i] = (float)(fy[y] * fx[flip ? W - 1 - x : x] * inv);
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int rg_bank_reid_batch(const unsigned char* bank_u8, int M, int Hs, int Ws, const int* idx, const int* params,
@@ -135,14 +201,14 @@ extern "C" int rg_bank_reid_batch(const unsigned char* bank_u8, int M, int Hs, i
     RG_REQUIRE(bank_u8 && idx && params && lut && fill && out, "rg_bank_reid_batch: null argument");
     RG_REQUIRE(M > 0 && Hs > 0 && Ws > 0 && N > 0 && H > 0 && W > 0 && pad >= 0, "rg_bank_reid_batch: bad sizes");
     RG_REQUIRE(H <= Hs + 2 * pad && W <= Ws + 2 * pad, "rg_bank_reid_batch: crop %dx%d larger than the padded plane", H, W);
-    return launch_image<true>("rg_bank_reid_batch", bank_u8, M, Hs, Ws, idx, params, 8, lut, fill, out, N, H, W, pad, stream);
+    return launch_image<KIND_REID>("rg_bank_reid_batch", bank_u8, M, Hs, Ws, idx, params, 8, lut, fill, out, N, H, W, pad, stream);
 }
 
 extern "C" int rg_bank_gan_batch(const unsigned char* bank_u8, int M, int Hg, int Wg, const int* idx, const int* flip,
                                  int flip_stride, const float* lut, float* out, int N, hipStream_t stream) {
     RG_REQUIRE(bank_u8 && idx && flip && lut && out, "rg_bank_gan_batch: null argument");
     RG_REQUIRE(M > 0 && Hg > 0 && Wg > 0 && N > 0 && flip_stride >= 0, "rg_bank_gan_batch: bad sizes");
-    return launch_image<false>("rg_bank_gan_batch", bank_u8, M, Hg, Wg, idx, flip, flip_stride, lut, nullptr, out, N, Hg, Wg, 0,
+    return launch_image<KIND_GAN>("rg_bank_gan_batch", bank_u8, M, Hg, Wg, idx, flip, flip_stride, lut, nullptr, out, N, Hg, Wg, 0,
                                stream);
 }
 
@@ -156,4 +222,25 @@ extern "C" int rg_bank_pose_batch(const int* centres, int M, int J, const int* i
     rg::ProfScope prof(rg::FAM_MISC, stream, 0.0, 4.0 * N * (double)J * Hg * Wg);
     hipLaunchKernelGGL(bank_pose_kernel, dim3(J, N), dim3(256), 0, stream, centres, M, idx, flip, flip_stride, sigma, out, J, Hg, Wg);
     return rg::check_launch("rg_bank_pose_batch");
+}
+
+extern "C" int rg_bank_fd_image_batch(const unsigned char* bank_u8, int M, int H, int W, const int* idx, const int* params,
+                                      const float* lut, float* out, int N, hipStream_t stream) {
+    RG_REQUIRE(bank_u8 && idx && params && lut && out, "rg_bank_fd_image_batch: null argument");
+    RG_REQUIRE(M > 0 && H > 0 && W > 0 && N > 0, "rg_bank_fd_image_batch: bad sizes");
+    return launch_image<KIND_FD>("rg_bank_fd_image_batch", bank_u8, M, H, W, idx, params, 8, lut, nullptr, out, N, H, W, 0, stream);
+}
+
+extern "C" int rg_bank_fd_pose_batch(const int* landmarks, int M, int J, const int* idx, const int* pose_params, float* out, int N,
+                                     int H, int W, hipStream_t stream) {
+    RG_REQUIRE(landmarks && idx && pose_params && out, "rg_bank_fd_pose_batch: null argument");
+    RG_REQUIRE(M > 0 && J > 0 && N > 0 && H > 0 && W > 0, "rg_bank_fd_pose_batch: bad sizes");
+    RG_REQUIRE(H <= MAXDIM && W <= MAXDIM, "rg_bank_fd_pose_batch: H, W must be <= %d", MAXDIM);
+    RG_REQUIRE(N <= 65535, "rg_bank_fd_pose_batch: N > 65535");
+    rg::ProfScope prof(rg::FAM_MISC, stream, 0.0, 4.0 * N * (double)J * H * W);
+    if ((W % 4 == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0))
+        hipLaunchKernelGGL(bank_fd_pose_kernel<4>, dim3(J, N), dim3(256), 0, stream, landmarks, M, idx, pose_params, out, J, H, W);
+    else
+        hipLaunchKernelGGL(bank_fd_pose_kernel<1>, dim3(J, N), dim3(256), 0, stream, landmarks, M, idx, pose_params, out, J, H, W);
+    return rg::check_launch("rg_bank_fd_pose_batch");
 }

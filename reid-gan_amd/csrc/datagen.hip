@@ -7,25 +7,12 @@
 //   RandomErasing rectangle fill    CC/clustercontrast/utils/data/transforms.py:52-96
 // The random draws (which joint to erase, sigma, rectangles, offsets, flips) stay on the host in the reference's own
 // order (`random` module), so a seeded run selects the same augmentations; the kernels apply them to the whole batch.
+#include "pose_profiles.h"
 #include "rg_common.h"
 
 namespace {
 
-constexpr int MAXDIM = 1024;      // H, W <= MAXDIM (profiles live in LDS)
-
-// scipy's 1-D Gaussian correlate of a unit impulse at `c` on [0, n) with 'reflect' extension (d c b a | a b c d | d c b a):
-// out[i] = sum_{k=-r..r} w[k] * [reflect(i + k) == c],  w[k] = exp(-k^2 / (2 sigma^2)) / sum_k(...)   (float64, as numpy)
-__device__ double impulse_response(int i, int c, int n, int r, double sigma, double wsum) {
-    double v = 0.0;
-    const double inv = -0.5 / (sigma * sigma);
-    int k = c - i;                                  // inside the array
-    if (k >= -r && k <= r) v += exp(inv * (double)k * (double)k) / wsum;
-    k = -1 - c - i;                                 // mirror image below 0: i + k = -1 - c
-    if (k >= -r && k <= r && i + k < 0) v += exp(inv * (double)k * (double)k) / wsum;
-    k = 2 * n - 1 - c - i;                          // mirror image above n-1: i + k = 2n - 1 - c
-    if (k >= -r && k <= r && i + k >= n) v += exp(inv * (double)k * (double)k) / wsum;
-    return v;
-}
+constexpr int MAXDIM = rg::POSE_MAXDIM;      // H, W <= MAXDIM (profiles live in LDS)
 
 // grid (J, N): one workgroup per (sample, joint).  mode 0: FD-GAN form, mode 1: plain Gaussian.
 __global__ __launch_bounds__(256) void pose_maps_kernel(const int* __restrict__ centers, const float* __restrict__ sigma,
@@ -45,35 +32,7 @@ __global__ __launch_bounds__(256) void pose_maps_kernel(const int* __restrict__ 
     }
     const double sg = (double)sigma[n];
     if (mode == 0) {
-        const int r = (int)(4.0 * sg + 0.5);                 // scipy: int(truncate * sd + 0.5)
-        // kernel normalisation sum_k exp(-k^2 / 2 sigma^2), summed in scipy's order (k ascending) by one thread
-        if (tid == 0) {
-            double acc = 0.0;
-            for (int k = -r; k <= r; ++k) acc += exp(-0.5 / (sg * sg) * (double)k * (double)k);
-            red[0] = acc;
-        }
-        __syncthreads();
-        const double wsum = red[0];
-        __syncthreads();
-        for (int i = tid; i < H; i += 256) fy[i] = impulse_response(i, cy, H, r, sg, wsum);
-        for (int i = tid; i < W; i += 256) fx[i] = impulse_response(i, cx, W, r, sg, wsum);
-        __syncthreads();
-        // map.max() = max(fy) * max(fx) (all entries >= 0)
-        double my = 0.0, mx = 0.0;
-        for (int i = tid; i < H; i += 256) my = fmax(my, fy[i]);
-        for (int i = tid; i < W; i += 256) mx = fmax(mx, fx[i]);
-        for (int off = 32; off > 0; off >>= 1) {
-            my = fmax(my, __shfl_xor(my, off, 64));
-            mx = fmax(mx, __shfl_xor(mx, off, 64));
-        }
-        if ((tid & 63) == 0) {
-            red[tid >> 6] = my;
-            red[4 + (tid >> 6)] = mx;
-        }
-        __syncthreads();
-        my = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-        mx = fmax(fmax(red[4], red[5]), fmax(red[6], red[7]));
-        const double inv = 1.0 / (my * mx);
+        const double inv = rg::fd_pose_profiles(fy, fx, red, cy, cx, H, W, sg);     // pose_profiles.h
         for (int i = tid; i < H * W; i += 256) {
             const int y = i / W, x = i - y * W;
             o[i] = (float)(fy[y] * fx[x] * inv);

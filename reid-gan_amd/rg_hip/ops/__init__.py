@@ -71,7 +71,8 @@ from .kmeans import (KMEANS_MAX_N, KMEANS_MAX_K, KMEANS_MAX_D, kmeans_rand_perm,
 from .optimizer import adam_advance, adam_step_dev, adam_step, sgd_step
 from .profile import profile_enable, check_not_profiling, profile_reset, profile_collect
 from .datagen import pose_maps, flip_pad_crop, erase_rects_
-from .databank import bank_lut, BankDraws, bank_draws, bank_reid_batch, bank_gan_batch, bank_pose_batch
+from .databank import (bank_lut, BankDraws, bank_draws, bank_reid_batch, bank_gan_batch, bank_pose_batch, FDDraws, fd_draws,
+                       bank_fd_image_batch, bank_fd_pose_batch)
 
 # ---- underscore names that code outside the package reads (rg_hip.nn / netgraph / parallel / lowp, the tests, tools/) ------------
 from ._base import _stream, _p, _chk, _pair, _ws_query, _ws_sizes
@@ -89,4 +90,4 @@ from .retrieval import _pair_vec
 from .dbscan import _chk_dbscan_matrix, _chk_dbscan_lists, _nbr_ptr
 from .infomap import _chk_infomap_table, _chk_infomap_graph, _infomap_level, _infomap_aggregate
 from .kmeans import _chk_kmeans_shape, _row_sqsum
-from .databank import _chk_bank, _chk_draws, _chk_lut
+from .databank import _chk_bank, _chk_draws, _chk_lut, _chk_fd_draws

@@ -2,7 +2,11 @@
 
 The indices and the augmentation draws are made on the host.  `bank_draws` packs them into ONE int32 host buffer (params [N, 8]
 followed by idx [N]) that crosses to the device in one copy; the three batch wrappers check the HOST copy against the geometry
-they are about to launch with and raise ValueError before anything is enqueued — a bad draw never reaches the device."""
+they are about to launch with and raise ValueError before anything is enqueued — a bad draw never reaches the device.
+
+FD-GAN stage II's two entries follow the same rule with a buffer of their own shape: `fd_draws` packs the image rows' params and
+indices and the map rows' pose params and indices into one int32 buffer (`FDDraws`), checked by `bank_fd_image_batch` and
+`bank_fd_pose_batch` before they launch."""
 from __future__ import absolute_import
 
 import torch
@@ -167,4 +171,168 @@ def bank_pose_batch(centres, draws, height, width, sigma=6.0):
     out = torch.empty((N, J, height, width), dtype=torch.float32, device=centres.device)
     lib.rg_bank_pose_batch(_p(centres), M, J, _p(draws.idx_dev), _p(draws.params_dev), 8, float(sigma), _p(out), N, height, width,
                            _stream())
+    return out
+
+
+# ---- FD-GAN stage II: rg_bank_fd_image_batch / rg_bank_fd_pose_batch ------------------------------------------------------------
+class FDDraws(object):
+    """One FD-GAN batch's rows and draws in ONE int32 host buffer, [params [Ni, 8] | idx [Ni] | pose_params [Np, 4] | pose_idx [Np]]:
+    `params` = (flip, 0, 0, er0, ec0, eh, ew, rgb) per image row, `pose_params` = (flip, sigma, erased joint or -1, 0) per map row
+    (either part may be empty), and after `to` the same four views of its single device copy."""
+
+    __slots__ = ("host", "idx", "params", "pose_idx", "pose_params", "idx_dev", "params_dev", "pose_idx_dev", "pose_params_dev", "_ok")
+
+    @staticmethod
+    def _ints(who, t, cols):
+        t = torch.as_tensor(t)
+        if t.numel() == 0:
+            t = torch.zeros((0,) if cols is None else (0, cols), dtype=torch.int64)
+        if t.is_cuda or t.dtype not in (torch.int32, torch.int64):
+            raise ValueError("fd_draws: %s must be a host tensor of int32 / int64 (the draws are checked on the host)" % who)
+        if cols is None:
+            t = t.reshape(-1)
+        elif t.dim() != 2 or t.shape[1] != cols:
+            raise ValueError("fd_draws: %s must be [N, %d]" % (who, cols))
+        if t.numel() and (int(t.min()) < -2 ** 31 or int(t.max()) >= 2 ** 31):
+            raise ValueError("fd_draws: %s does not fit int32" % who)
+        return t
+
+    def __init__(self, idx=None, params=None, pose_idx=None, pose_params=None):
+        idx = self._ints("idx", [] if idx is None else idx, None)
+        pose_idx = self._ints("pose_idx", [] if pose_idx is None else pose_idx, None)
+        ni, npose = idx.numel(), pose_idx.numel()
+        if ni + npose == 0:
+            raise ValueError("fd_draws: an empty batch")
+        host = self.host = torch.zeros(ni * 9 + npose * 5, dtype=torch.int32)
+        self.params, self.idx = host[:ni * 8].view(ni, 8), host[ni * 8:ni * 9]
+        self.pose_params, self.pose_idx = host[ni * 9:ni * 9 + npose * 4].view(npose, 4), host[ni * 9 + npose * 4:]
+        self.idx.copy_(idx)
+        self.pose_idx.copy_(pose_idx)
+        if params is not None:
+            params = self._ints("params", params, 8)
+            if params.shape[0] != ni:
+                raise ValueError("fd_draws: %d rows of params for %d image rows" % (params.shape[0], ni))
+            self.params.copy_(params)
+        if pose_params is not None:
+            pose_params = self._ints("pose_params", pose_params, 4)
+            if pose_params.shape[0] != npose:
+                raise ValueError("fd_draws: %d rows of pose_params for %d map rows" % (pose_params.shape[0], npose))
+            self.pose_params.copy_(pose_params)
+        elif npose:
+            raise ValueError("fd_draws: pose_idx without pose_params (sigma has no default)")
+        self.idx_dev = self.params_dev = self.pose_idx_dev = self.pose_params_dev = None
+        self._ok = set()
+
+    def to(self, device):
+        """the one host->device copy of the batch"""
+        ni, npose = self.idx.numel(), self.pose_idx.numel()
+        dev = self.host.to(device, non_blocking=True)
+        self.params_dev, self.idx_dev = dev[:ni * 8].view(ni, 8), dev[ni * 8:ni * 9]
+        self.pose_params_dev, self.pose_idx_dev = dev[ni * 9:ni * 9 + npose * 4].view(npose, 4), dev[ni * 9 + npose * 4:]
+        return self
+
+    def check_images(self, who, M, H, W):
+        """ValueError unless there is an image row, 0 <= idx < M, flip in {0, 1}, every rectangle (eh > 0) has ew > 0 and lies inside
+        [0, H) x [0, W), and 0 <= rgb < 2^24."""
+        key = ("image", M, H, W)
+        if key in self._ok:
+            return
+        idx, p = self.idx, self.params
+        if idx.numel() == 0:
+            raise ValueError("%s: the draws hold no image rows" % who)
+        if int(idx.min()) < 0 or int(idx.max()) >= M:
+            raise ValueError("%s: bank row index outside [0, %d)" % (who, M))
+        if bool(((p[:, 0] != 0) & (p[:, 0] != 1)).any()):
+            raise ValueError("%s: flip must be 0 or 1" % who)
+        er0, ec0, eh, ew = p[:, 3].long(), p[:, 4].long(), p[:, 5].long(), p[:, 6].long()
+        if bool((eh < 0).any()) or bool((ew < 0).any()):
+            raise ValueError("%s: negative patch size" % who)
+        on = eh > 0
+        if bool((on & ((ew <= 0) | (er0 < 0) | (ec0 < 0) | (er0 + eh > H) | (ec0 + ew > W))).any()):
+            raise ValueError("%s: patch outside the %dx%d plane" % (who, H, W))
+        if bool(((p[:, 7] < 0) | (p[:, 7] >= 2 ** 24)).any()):
+            raise ValueError("%s: rgb must be R | G << 8 | B << 16 in [0, 2^24)" % who)
+        self._ok.add(key)
+
+    def check_poses(self, who, M, J, H, W):
+        """ValueError unless there is a map row, at most 65535 of them, 0 <= pose_idx < M, flip in {0, 1}, sigma >= 1 with
+        int(4 sigma + 0.5) <= min(H, W) (the closed form holds the first mirror image only) and -1 <= erased joint < J."""
+        key = ("pose", M, J, H, W)
+        if key in self._ok:
+            return
+        idx, p = self.pose_idx, self.pose_params
+        if idx.numel() == 0:
+            raise ValueError("%s: the draws hold no map rows" % who)
+        if idx.numel() > 65535:
+            raise ValueError("%s: at most 65535 samples per launch" % who)
+        if int(idx.min()) < 0 or int(idx.max()) >= M:
+            raise ValueError("%s: landmark row index outside [0, %d)" % (who, M))
+        if bool(((p[:, 0] != 0) & (p[:, 0] != 1)).any()):
+            raise ValueError("%s: flip must be 0 or 1" % who)
+        sig = p[:, 1].long()
+        if bool((sig < 1).any()):
+            raise ValueError("%s: sigma must be an integer >= 1" % who)
+        if int(4.0 * int(sig.max()) + 0.5) > min(H, W):
+            raise ValueError("%s: sigma %d needs a radius of %d > min(%d, %d): only the first mirror image is modelled"
+                             % (who, int(sig.max()), int(4.0 * int(sig.max()) + 0.5), H, W))
+        if bool(((p[:, 2] < -1) | (p[:, 2] >= J)).any()):
+            raise ValueError("%s: erased joint outside [-1, %d)" % (who, J))
+        self._ok.add(key)
+
+
+def fd_draws(idx=None, params=None, pose_idx=None, pose_params=None, device=None):
+    """FDDraws of host image rows `idx` [Ni] with `params` [Ni, 8] (None: all zero) and map rows `pose_idx` [Np] with `pose_params`
+    [Np, 4], uploaded when `device` is given."""
+    d = FDDraws(idx, params, pose_idx, pose_params)
+    return d if device is None else d.to(device)
+
+
+def _chk_fd_draws(who, draws, device):
+    if not isinstance(draws, FDDraws):
+        raise TypeError("%s: draws must come from ops.fd_draws (they are checked on the host before the launch)" % who)
+    if draws.idx_dev is None:
+        draws.to(device)
+    if draws.idx_dev.device != device:
+        raise RuntimeError("%s: the draws were uploaded to %s, the bank lives on %s" % (who, draws.idx_dev.device, device))
+    return draws
+
+
+def bank_fd_image_batch(bank_u8, draws, lut):
+    """[Ni, 3, H, W] fp32: FD-GAN stage II's RectScale'd planes `bank_u8` [M, H, W, 3] -> RandomSizedEarser's colour patch (on the
+    bytes) -> flip -> ToTensor -> Normalize of the rows draws.idx with draws.params [Ni, 8] = (flip, 0, 0, er0, ec0, eh, ew, rgb);
+    one launch (rg_bank_fd_image_batch)."""
+    if not torch.is_tensor(bank_u8) or bank_u8.dtype != torch.uint8 or bank_u8.dim() != 4 or bank_u8.shape[3] != 3:
+        raise ValueError("bank_fd_image_batch: the bank must be a uint8 tensor [M, H, W, 3]")
+    M, H, W = bank_u8.shape[0], bank_u8.shape[1], bank_u8.shape[2]
+    if not isinstance(draws, FDDraws):
+        raise TypeError("bank_fd_image_batch: draws must come from ops.fd_draws (they are checked on the host before the launch)")
+    draws.check_images("bank_fd_image_batch", M, H, W)           # the draws first: a bad one is refused wherever the bank lives
+    bank_u8 = _chk_bank("bank_fd_image_batch", bank_u8)
+    draws = _chk_fd_draws("bank_fd_image_batch", draws, bank_u8.device)
+    lut = _chk_lut("bank_fd_image_batch", lut)
+    N = draws.idx.numel()
+    out = torch.empty((N, 3, H, W), dtype=torch.float32, device=bank_u8.device)
+    lib.rg_bank_fd_image_batch(_p(bank_u8), M, H, W, _p(draws.idx_dev), _p(draws.params_dev), _p(lut), _p(out), N, _stream())
+    return out
+
+
+def bank_fd_pose_batch(landmarks, draws, height, width):
+    """[Np, J, H, W] fp32 FD-GAN pose maps of the rows draws.pose_idx of the int32 landmark table [M, J, 2] = (row, col) (-1: not
+    detected) with draws.pose_params [Np, 4] = (flip, sigma, erased joint or -1, 0): pose_maps(mode=0) + flip_images on the gathered
+    landmarks, in one launch (rg_bank_fd_pose_batch)."""
+    if not torch.is_tensor(landmarks) or landmarks.dtype != torch.int32 or landmarks.dim() != 3 or landmarks.shape[2] != 2:
+        raise ValueError("bank_fd_pose_batch: landmarks must be an int32 tensor [M, J, 2]")
+    M, J = landmarks.shape[0], landmarks.shape[1]
+    height, width = int(height), int(width)
+    if not (0 < height <= 1024 and 0 < width <= 1024):
+        raise ValueError("bank_fd_pose_batch: map size must be within 1024x1024")
+    if not isinstance(draws, FDDraws):
+        raise TypeError("bank_fd_pose_batch: draws must come from ops.fd_draws (they are checked on the host before the launch)")
+    draws.check_poses("bank_fd_pose_batch", M, J, height, width)
+    landmarks = _chk_rr(landmarks, "landmarks", dtype=torch.int32, dim=3)
+    draws = _chk_fd_draws("bank_fd_pose_batch", draws, landmarks.device)
+    N = draws.pose_idx.numel()
+    out = torch.empty((N, J, height, width), dtype=torch.float32, device=landmarks.device)
+    lib.rg_bank_fd_pose_batch(_p(landmarks), M, J, _p(draws.pose_idx_dev), _p(draws.pose_params_dev), _p(out), N, height, width,
+                              _stream())
     return out
