@@ -840,6 +840,30 @@ int rg_bank_fd_image_batch(const unsigned char* bank_u8, int M, int H, int W, co
  * workgroup per (sample, joint), 16-byte row stores where W % 4 == 0; N <= 65535, H, W <= 1024. */
 int rg_bank_fd_pose_batch(const int* landmarks, int M, int J, const int* idx, const int* pose_params, float* out, int N, int H,
                           int W, rg_stream_t stream);
+/* FD-GAN stage I's images (FD/baseline.py:39-45: RandomSizedRectCrop -> RandomSizedEarser -> RandomHorizontalFlip -> ToTensor ->
+ * Normalize) from a RAW bank: every image at its own size, bank_u8 + offsets[m] = [H_m][W_m][3] interleaved RGB bytes with
+ * sizes[m] = (H_m, W_m).  The crop is `img.crop(box).resize((W, H), BILINEAR)`: the resize FOLLOWS the draw, so the kernel
+ * resamples the box itself, with PIL's integer rule — a horizontal pass over the box's rows to a uint8 intermediate, a vertical
+ * pass over that, each  out = min(255, (2^21 + sum_x in[lo + x] * k_x) >> 22).  The resample box is always the whole crop, so
+ * (lo, cnt, k) of an axis depend on (input length, output length) only; the host builds them once in float64
+ * (clustercontrast/utils/data/device_bank.py pil_bilinear_table): table_x holds (nmax_x + 1) * W rows of stride_x ints
+ * (lo, cnt, k_0 .. k_{stride_x - 3}), row (n, j) for input length n and output column j at (n * W + j) * stride_x; table_y likewise
+ * (nmax_y + 1) * H rows for input length n and output row j.  draws[N][12] int32 = (bank row, x1, y1, w, h, flip, er0, ec0, eh, ew,
+ * rgb, 0): the box's left / upper corner and size in the image, the eraser's patch in the H x W output BEFORE the flip and its
+ * colour R | G << 8 | B << 16; for out[n][c][r][x]:
+ *     xs = flip ? W-1-x : x
+ *     eh > 0 and (r, xs) in [er0, er0+eh) x [ec0, ec0+ew)  -> lut[c][byte c of rgb]
+ *     otherwise                                            -> lut[c][two-pass resample of the box at (r, xs), channel c]
+ * No floating-point arithmetic, no atomic, ONE launch, no intermediate in global memory: a workgroup keeps the horizontally
+ * resampled bytes of its output columns in LDS ([3][h][columns]).  hmax >= every draw's h sizes that tile: a workgroup takes a strip of
+ * output columns, the largest multiple of 4 up to 32 whose hmax x columns x 3 bytes fit 60 KiB (a whole sample where W is no wider).  rg_bank_fd_crop_regime returns
+ * the columns per workgroup (a value, not a status: W = whole samples, less = strips, -1 = W no multiple of 4 or no strip fits).
+ * W % 4 == 0 (16-byte row stores), N <= 65535.  The wrapper (rg_hip/ops/databank.py) refuses every draw outside its image before
+ * the launch; the kernel additionally reads nothing for such a sample (it comes out as normalised black under its patch). */
+int64_t rg_bank_fd_crop_regime(int hmax, int W);
+int rg_bank_fd_crop_batch(const unsigned char* bank_u8, const int64_t* offsets, const int* sizes, int M, const int* table_x,
+                          int stride_x, int nmax_x, const int* table_y, int stride_y, int nmax_y, const int* draws, const float* lut,
+                          float* out, int N, int H, int W, int hmax, rg_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,10 @@ at 256x128 / 128x64: Market-1501's 35 585 images are 4.4 GB, MSMT17's 126 441 ar
 view with nothing but the row indices and the draws crossing from the host.  The pose centres (`cords_to_map`'s per-point
 arithmetic, device_pose._centres) are likewise computed once per image into an int32 device table.
 
+One loader's resize FOLLOWS its draw (FD-GAN stage I's RandomSizedRectCrop): `DeviceRawBank` keeps the decoded images at their own
+size with PIL's bilinear coefficients as integer tables (`pil_bilinear_table`), and the batch kernel resamples the drawn box
+(reid/utils/data/device_stage1.py).
+
 Not here, still the reference's: JPEG decoding itself (PIL, at build time) and the data sets' directory parsing.
 
 Importable without a reference tree, without torchvision and without pandas; PIL is needed by `from_files` only.
@@ -95,6 +99,16 @@ def _decode(path, reid_size, gan_size, reid_resample="bicubic"):
     return out_r, out_g, old
 
 
+def _decode_pool(one, M, workers):
+    """one(m) for every m in [0, M) on `workers` threads (PIL releases the GIL while it decodes and resamples)"""
+    if workers == 1:
+        for m in range(M):
+            one(m)
+    else:
+        with ThreadPoolExecutor(max_workers=workers) as pool:
+            list(pool.map(one, range(M), chunksize=1))
+
+
 def stage_files(entries, root=None, reid_size=(256, 128), gan_size=(128, 64), pose_file=None, workers=None, reid_resample="bicubic",
                 pose_root=None):
     """Decode every file of `entries` = [(fname, pid, camid)] ONCE and resize it to both plane sizes on the host.  Returns the
@@ -124,12 +138,7 @@ def stage_files(entries, root=None, reid_size=(256, 128), gan_size=(128, 64), po
             gan[m] = g
         old[m] = o
 
-    if workers == 1:
-        for m in range(M):
-            one(m)
-    else:                                                   # PIL releases the GIL while it decodes and resamples
-        with ThreadPoolExecutor(max_workers=workers) as pool:
-            list(pool.map(one, range(M), chunksize=1))
+    _decode_pool(one, M, workers)
     cords = None
     if pose_file is not None:
         table = read_pose_csv(pose_file)
@@ -215,6 +224,119 @@ class DeviceImageBank(object):
         host (`stage_files`) and upload."""
         return cls.from_arrays(device=device, **stage_files(entries, root, reid_size, gan_size, pose_file, workers, reid_resample,
                                                             pose_root))
+
+
+# ---- the raw bank (FD-GAN stage I) ----------------------------------------------------------------------------------------------
+PIL_PRECISION_BITS = 22
+RAW_MAX_RATIO = 8                                           # input length / output length: keeps a table row at 17 taps
+
+
+def pil_bilinear_table(nmax, m):
+    """int32 [nmax + 1, m, 2 + K]: PIL's BILINEAR coefficients of an axis resampled from input length n (the first index; row 0 is
+    unused) to output length m over its WHOLE extent, as rows (lo, cnt, k_0 .. k_{K-1}) — the taps in[lo .. lo + cnt) with
+    integer weights k_x (zero beyond cnt), K the longest row.  The rule, in float64 throughout (checked against PIL's output, byte for byte):
+        scale = n / m; fs = max(scale, 1); support = fs; centre = (j + 0.5) * scale
+        lo = max(int(centre - support + 0.5), 0); hi = min(int(centre + support + 0.5), n)          (int truncates)
+        w_x = 1 - a if a < 1 else 0,  a = |(x + lo - centre + 0.5) * (1 / fs)|;  ww = sum of w_x in increasing x
+        k_x = int(0.5 + (w_x / ww) * 2^22)
+    and a resampled byte is min(255, (2^21 + sum_x in[lo + x] * k_x) >> 22).  All input lengths at once; only the sum runs over
+    x in order."""
+    nmax, m = int(nmax), int(m)
+    if nmax < 1 or m < 1 or nmax > RAW_MAX_RATIO * m:
+        raise ValueError("pil_bilinear_table: input lengths up to %d for output length %d (at most %d times as long)"
+                         % (nmax, m, RAW_MAX_RATIO))
+    n = np.arange(1, nmax + 1, dtype=np.int64)[:, None]
+    scale = n.astype(np.float64) / np.float64(m)
+    fs = np.maximum(scale, 1.0)
+    centre = (np.arange(m, dtype=np.float64)[None, :] + 0.5) * scale
+    lo = np.maximum((centre - fs + 0.5).astype(np.int64), 0)
+    hi = np.minimum((centre + fs + 0.5).astype(np.int64), n)
+    cnt = hi - lo
+    K = int(cnt.max())
+    x = np.arange(K, dtype=np.int64)[None, None, :]
+    a = np.abs(((x + lo[:, :, None]).astype(np.float64) - centre[:, :, None] + 0.5) * (1.0 / fs)[:, :, None])
+    w = np.where((a < 1.0) & (x < cnt[:, :, None]), 1.0 - a, 0.0)
+    ww = np.zeros_like(centre)
+    for i in range(K):                                      # PIL sums in increasing x; adding the zeros beyond cnt changes nothing
+        ww = ww + w[:, :, i]
+    k = (0.5 + (w / ww[:, :, None]) * np.float64(1 << PIL_PRECISION_BITS)).astype(np.int64)
+    table = np.zeros((nmax + 1, m, 2 + K), dtype=np.int32)
+    table[1:, :, 0], table[1:, :, 1], table[1:, :, 2:] = lo, cnt, k
+    return table
+
+
+class DeviceRawBank(object):
+    """Every image of a data set at its OWN size on the device, for loaders whose resize follows the draw (FD-GAN stage I's
+    RandomSizedRectCrop): `data` uint8 [sum H_m W_m 3] (HWC images one after the other), `offsets` int64 [M] (bytes), `sizes` int32
+    [M, 2] = (H_m, W_m) with its host copy `sizes_host`, and PIL's bilinear coefficient tables `table_x` / `table_y`
+    (pil_bilinear_table) for every input length up to the widest / highest image at the output `size` = (height, width); plus the
+    host bookkeeping of DeviceImageBank (`fnames`, `pids`, `camids`, `row`: fname -> bank row).  Market-1501's trainval (12 936
+    images of 128x64) is 318 MB."""
+
+    def __init__(self, data, offsets, sizes, sizes_host, table_x, table_y, size, fnames, pids, camids):
+        self.data, self.offsets, self.sizes, self.sizes_host = data, offsets, sizes, sizes_host
+        self.table_x, self.table_y, self.size = table_x, table_y, (int(size[0]), int(size[1]))
+        self.fnames, self.pids, self.camids = list(fnames), list(pids), list(camids)
+        self.row = {f: m for m, f in enumerate(self.fnames)}
+        if len(self.row) != len(self.fnames):
+            raise ValueError("DeviceRawBank: duplicate file names")
+        self.device = data.device
+
+    def __len__(self):
+        return len(self.fnames)
+
+    @property
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in (self.data, self.offsets, self.sizes, self.table_x, self.table_y))
+
+    @classmethod
+    def from_arrays(cls, images, fnames, pids, camids, device=None, size=(256, 128)):
+        """From decoded images, a list of HWC uint8 arrays [H_m, W_m, 3]; size = (height, width) of the batches.  An image more
+        than 8 times as high or wide as the output is refused by name (its coefficient rows would outgrow the kernel's)."""
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        device = torch.device(device)
+        height, width = int(size[0]), int(size[1])
+        if height < 1 or width < 1:
+            raise ValueError("DeviceRawBank: output size %r" % (size,))
+        if not (len(images) == len(fnames) == len(pids) == len(camids)) or not len(fnames):
+            raise ValueError("DeviceRawBank: images, fnames, pids and camids must be non-empty and of one length")
+        arrays = []
+        for a, f in zip(images, fnames):
+            a = np.asarray(a)
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+                raise ValueError("DeviceRawBank: %s must be uint8 [H, W, 3], got %s %s" % (f, a.dtype, a.shape))
+            if a.shape[0] > RAW_MAX_RATIO * height or a.shape[1] > RAW_MAX_RATIO * width:
+                raise ValueError("DeviceRawBank: %s is %dx%d, more than %d times the %dx%d output"
+                                 % (f, a.shape[0], a.shape[1], RAW_MAX_RATIO, height, width))
+            arrays.append(a)
+        sizes = np.asarray([a.shape[:2] for a in arrays], dtype=np.int32)
+        nbytes = sizes[:, 0].astype(np.int64) * sizes[:, 1] * 3
+        offsets = np.concatenate([[0], np.cumsum(nbytes)[:-1]]).astype(np.int64)
+        data = np.concatenate([a.reshape(-1) for a in arrays])
+        table_x = pil_bilinear_table(int(sizes[:, 1].max()), width)
+        table_y = pil_bilinear_table(int(sizes[:, 0].max()), height)
+        return cls(torch.from_numpy(data).to(device), torch.from_numpy(offsets).to(device), torch.from_numpy(sizes).to(device),
+                   sizes, torch.from_numpy(table_x).to(device), torch.from_numpy(table_y).to(device), (height, width), fnames, pids,
+                   camids)
+
+    @classmethod
+    def from_files(cls, entries, root=None, workers=None, device=None, size=(256, 128)):
+        """Decode each file of the reference's (fname, pid, camid) triples once, with the reference's call
+        (`Image.open(path).convert('RGB')`) on the decode threads of `stage_files`, and upload the images as they are."""
+        entries = list(entries)
+        if not entries:
+            raise ValueError("DeviceRawBank: no entries")
+        paths = [f if root is None else osp.join(root, f) for f, _, _ in entries]
+        images = [None] * len(entries)
+
+        def one(m):
+            from PIL import Image
+            images[m] = np.asarray(Image.open(paths[m]).convert("RGB"), dtype=np.uint8)
+
+        _decode_pool(one, len(entries), default_workers() if workers is None else max(1, int(workers)))
+        return cls.from_arrays(images, [e[0] for e in entries], [int(e[1]) for e in entries], [int(e[2]) for e in entries], device,
+                               size)
 
 
 # ---- loaders ------------------------------------------------------------------------------------------------------------------

@@ -193,6 +193,102 @@ __global__ __launch_bounds__(256) void bank_fd_pose_kernel(const int* __restrict
     }
 }
 
+// ---- FD-GAN stage I: RandomSizedRectCrop -> RandomSizedEarser -> flip -> ToTensor -> Normalize from the RAW images -------------
+// The resize follows the draw here (img.crop(box).resize((W, H), BILINEAR)), so there is no resized plane to gather from: the
+// kernel resamples the drawn box itself, with PIL's own integer rule.  PIL's coefficients of an axis depend on (input length,
+// output length) alone because the resample box is always the whole crop; the host builds them once for every input length that
+// can occur (device_bank.pil_bilinear_table) as rows of `stride` ints (lo, cnt, k_0 .. k_{stride-3}), row (n, j) at
+// (n * out_len + j) * stride, and the device does integer multiply-adds only:
+//     out = min(255, (2^21 + sum_x in[lo + x] * k_x) >> 22)        (k_x >= 0, so the sum is never negative)
+// grid (strips, N).  A workgroup takes SW neighbouring PRE-FLIP output columns of one sample: pass 1 resamples the crop's h rows
+// to those columns into an LDS tile of bytes [3][h][SW] (planar, so four neighbouring columns of a channel are one dword),
+// pass 2 resamples the tile's columns to the H output rows, lays the eraser's patch over the bytes, looks them up in the
+// Normalize table and writes 4 columns per thread with one 16-byte store (reversed for a flipped sample).  SW is the
+// largest multiple of 4 up to FD_CROP_COLS whose tile of hmax rows fits FD_CROP_LDS; an output no wider than that is one
+// workgroup per sample, anything else is cut into strips (the recipe's 128 columns into 4: 119 us against 220 us for 512 samples
+// from one workgroup each, profiles/fd_stage1_loader.txt).
+constexpr int FD_CROP_LDS = 60 * 1024;      // the tile's share of a 64 KiB workgroup, so two workgroups fit a CU's 160 KiB
+constexpr int FD_CROP_INTS = 12;            // (row, x1, y1, w, h, flip, er0, ec0, eh, ew, rgb, -) per sample
+constexpr int FD_CROP_BITS = 22;
+
+constexpr int FD_CROP_COLS = 32;            // widest strip: 4 strips of a 128-column sample keep 8 workgroups on a CU, not 2
+
+// columns per workgroup for crops of up to hmax rows: W (one workgroup per sample), a smaller multiple of 4 (strips), 0 (none fits)
+int fd_crop_strip(int hmax, int W) {
+    int sw = (FD_CROP_LDS / (3 * hmax)) & ~3;
+    if (sw > FD_CROP_COLS) sw = FD_CROP_COLS;
+    return sw >= W ? W : sw;
+}
+
+__global__ __launch_bounds__(256) void bank_fd_crop_kernel(const unsigned char* __restrict__ bank, const int64_t* __restrict__ offs,
+                                                           const int* __restrict__ sizes, int M, const int* __restrict__ tabx,
+                                                           int sx, int nx, const int* __restrict__ taby, int sy, int ny,
+                                                           const int* __restrict__ draws, const float* __restrict__ lut_g,
+                                                           float* __restrict__ out, int H, int W, int SW, int hmax) {
+    extern __shared__ __align__(16) unsigned char tile[];        // [3][h][SW] bytes of pass 1
+    __shared__ float lut[768];
+    const int tid = threadIdx.x, n = blockIdx.y;
+    const int c0 = blockIdx.x * SW;                              // first pre-flip output column of this strip
+    const int sw = min(SW, W - c0);
+    for (int i = tid; i < 768; i += 256) lut[i] = lut_g[i];
+    const int* d = draws + (int64_t)n * FD_CROP_INTS;
+    const int m = d[0], x1 = d[1], y1 = d[2], w = d[3], flip = d[5];
+    const int er0 = d[6], ec0 = d[7], eh = d[8], ew = d[9], rgb = d[10];
+    int h = d[4];
+    // the wrapper refuses every draw outside the image before the launch; here such a sample reads nothing and comes out black
+    bool ok = (unsigned)m < (unsigned)M && w >= 1 && h >= 1 && w <= nx && h <= ny && h <= hmax && x1 >= 0 && y1 >= 0;
+    int Wm = 0;
+    if (ok) {
+        Wm = sizes[2 * m + 1];
+        ok = y1 <= sizes[2 * m] - h && x1 <= Wm - w;
+    }
+    if (!ok) h = 0;
+    if (ok) {
+        const unsigned char* src = bank + offs[m] + ((int64_t)y1 * Wm + x1) * 3;
+        const int* tx = tabx + ((int64_t)w * W + c0) * sx;
+        for (int i = tid; i < h * sw * 3; i += 256) {
+            const int cc = i % sw, t = i / sw;
+            const int ch = t % 3, row = t / 3;
+            const int* e = tx + cc * sx;
+            const int cnt = e[1];
+            const unsigned char* p = src + ((int64_t)row * Wm + e[0]) * 3 + ch;
+            int acc = 1 << (FD_CROP_BITS - 1);
+            for (int x = 0; x < cnt; ++x) acc += (int)p[x * 3] * e[2 + x];
+            tile[(ch * h + row) * SW + cc] = (unsigned char)min(acc >> FD_CROP_BITS, 255);
+        }
+    }
+    __syncthreads();
+    const int* ty = taby + (int64_t)h * H * sy;
+    const int groups = sw >> 2;
+    for (int i = tid; i < 3 * H * groups; i += 256) {
+        const int q = i % groups, t = i / groups;
+        const int r = t % H, ch = t / H;
+        int acc[4] = {1 << (FD_CROP_BITS - 1), 1 << (FD_CROP_BITS - 1), 1 << (FD_CROP_BITS - 1), 1 << (FD_CROP_BITS - 1)};
+        if (ok) {
+            const int* e = ty + r * sy;
+            const int lo = e[0], cnt = e[1];
+            for (int x = 0; x < cnt; ++x) {
+                const unsigned v = *reinterpret_cast<const unsigned*>(tile + (ch * h + lo + x) * SW + 4 * q);
+                const int k = e[2 + x];
+                for (int j = 0; j < 4; ++j) acc[j] += (int)((v >> (8 * j)) & 255u) * k;
+            }
+        }
+        const int cp = c0 + 4 * q;                               // pre-flip columns cp .. cp + 3
+        const bool in_rows = eh > 0 && r >= er0 && r < er0 + eh;
+        float f[4];
+        for (int j = 0; j < 4; ++j) {
+            int b = min(acc[j] >> FD_CROP_BITS, 255);
+            if (in_rows && cp + j >= ec0 && cp + j < ec0 + ew) b = (rgb >> (8 * ch)) & 255;
+            f[j] = lut[ch * 256 + b];
+        }
+        float* o = out + (((int64_t)n * 3 + ch) * H + r) * W;
+        if (flip)
+            *reinterpret_cast<float4*>(o + (W - 4 - cp)) = make_float4(f[3], f[2], f[1], f[0]);
+        else
+            *reinterpret_cast<float4*>(o + cp) = make_float4(f[0], f[1], f[2], f[3]);
+    }
+}
+
 }  // namespace
 
 extern "C" int rg_bank_reid_batch(const unsigned char* bank_u8, int M, int Hs, int Ws, const int* idx, const int* params,
@@ -243,4 +339,29 @@ extern "C" int rg_bank_fd_pose_batch(const int* landmarks, int M, int J, const i
     else
         hipLaunchKernelGGL(bank_fd_pose_kernel<1>, dim3(J, N), dim3(256), 0, stream, landmarks, M, idx, pose_params, out, J, H, W);
     return rg::check_launch("rg_bank_fd_pose_batch");
+}
+
+extern "C" int64_t rg_bank_fd_crop_regime(int hmax, int W) {
+    if (hmax <= 0 || W <= 0 || (W & 3)) return -1;
+    const int sw = fd_crop_strip(hmax, W);
+    return sw >= 4 ? sw : -1;
+}
+
+extern "C" int rg_bank_fd_crop_batch(const unsigned char* bank_u8, const int64_t* offsets, const int* sizes, int M, const int* table_x,
+                                     int stride_x, int nmax_x, const int* table_y, int stride_y, int nmax_y, const int* draws,
+                                     const float* lut, float* out, int N, int H, int W, int hmax, hipStream_t stream) {
+    RG_REQUIRE(bank_u8 && offsets && sizes && table_x && table_y && draws && lut && out, "rg_bank_fd_crop_batch: null argument");
+    RG_REQUIRE(M > 0 && N > 0 && H > 0 && W > 0 && nmax_x > 0 && nmax_y > 0, "rg_bank_fd_crop_batch: bad sizes");
+    RG_REQUIRE(stride_x >= 3 && stride_y >= 3, "rg_bank_fd_crop_batch: a table row holds (lo, cnt, k_0 ...)");
+    RG_REQUIRE(W % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0,
+               "rg_bank_fd_crop_batch: W must be a multiple of 4 and out 16-byte aligned (16-byte row stores)");
+    RG_REQUIRE(N <= 65535, "rg_bank_fd_crop_batch: N > 65535");
+    RG_REQUIRE(hmax >= 1 && hmax <= nmax_y, "rg_bank_fd_crop_batch: hmax %d outside [1, %d]", hmax, nmax_y);
+    const int sw = fd_crop_strip(hmax, W);
+    RG_REQUIRE(sw >= 4, "rg_bank_fd_crop_batch: a 4-column strip of %d rows does not fit %d bytes of LDS", hmax, FD_CROP_LDS);
+    const int strips = (W + sw - 1) / sw;
+    rg::ProfScope prof(rg::FAM_MISC, stream, 0.0, 12.0 * N * (double)H * W + 3.0 * N * (double)H * W);
+    hipLaunchKernelGGL(bank_fd_crop_kernel, dim3(strips, N), dim3(256), (size_t)3 * hmax * sw, stream, bank_u8, offsets, sizes, M,
+                       table_x, stride_x, nmax_x, table_y, stride_y, nmax_y, draws, lut, out, H, W, sw, hmax);
+    return rg::check_launch("rg_bank_fd_crop_batch");
 }

@@ -23,8 +23,9 @@ The paste rule.  The reference's eraser ends in `img.paste(I, part1.size)`: the 
 patch lands with its upper-left corner at column pw, row ph — not at the box it was sized from — and PIL clips it to the image.
 That is reproduced as it is: rows [ph, min(H, 2 ph)), columns [pw, min(W, 2 pw)), in the coordinates before the flip.
 
-Still the reference's, on the host: JPEG decoding (once, at build time), the data sets' directory parsing, and stage I's
-`RandomSizedRectCrop` (a fresh resample per draw; baseline.py keeps its host loader).
+Still the reference's, on the host: JPEG decoding (once, at build time) and the data sets' directory parsing.  Stage I's
+`RandomSizedRectCrop` resamples a fresh box per draw, so it cannot gather from these planes: `baseline.py`'s loader is
+device_stage1.py, on a raw bank with the resampling in the kernel; it shares the sampler, the eraser and the test loader of this file.
 
 Importable without a reference tree and without torchvision; there is deliberately no sampler.py / preprocessor.py / transforms.py
 next to this file — those names resolve to the reference's modules behind the overlay.

@@ -72,7 +72,8 @@ from .optimizer import adam_advance, adam_step_dev, adam_step, sgd_step
 from .profile import profile_enable, check_not_profiling, profile_reset, profile_collect
 from .datagen import pose_maps, flip_pad_crop, erase_rects_
 from .databank import (bank_lut, BankDraws, bank_draws, bank_reid_batch, bank_gan_batch, bank_pose_batch, FDDraws, fd_draws,
-                       bank_fd_image_batch, bank_fd_pose_batch)
+                       bank_fd_image_batch, bank_fd_pose_batch, FD_CROP_WHOLE, FD_CROP_STRIPS, FD_CROP_INTS, fd_crop_strip_width, fd_crop_regime,
+                       FDCropDraws, fd_crop_draws, bank_fd_crop_batch)
 
 # ---- underscore names that code outside the package reads (rg_hip.nn / netgraph / parallel / lowp, the tests, tools/) ------------
 from ._base import _stream, _p, _chk, _pair, _ws_query, _ws_sizes

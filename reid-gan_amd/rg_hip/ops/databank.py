@@ -6,7 +6,11 @@ they are about to launch with and raise ValueError before anything is enqueued â
 
 FD-GAN stage II's two entries follow the same rule with a buffer of their own shape: `fd_draws` packs the image rows' params and
 indices and the map rows' pose params and indices into one int32 buffer (`FDDraws`), checked by `bank_fd_image_batch` and
-`bank_fd_pose_batch` before they launch."""
+`bank_fd_pose_batch` before they launch.
+
+FD-GAN stage I reads a RAW bank (every image at its own size) and resamples the drawn box in the kernel: `fd_crop_draws` packs the
+rows, boxes, flips and patches into one int32 buffer [N, 12] (`FDCropDraws`), checked by `bank_fd_crop_batch` against the host copy
+of the bank's size table before it launches."""
 from __future__ import absolute_import
 
 import torch
@@ -335,4 +339,113 @@ def bank_fd_pose_batch(landmarks, draws, height, width):
     out = torch.empty((N, J, height, width), dtype=torch.float32, device=landmarks.device)
     lib.rg_bank_fd_pose_batch(_p(landmarks), M, J, _p(draws.pose_idx_dev), _p(draws.pose_params_dev), _p(out), N, height, width,
                               _stream())
+    return out
+
+
+# ---- FD-GAN stage I: rg_bank_fd_crop_batch --------------------------------------------------------------------------------------
+FD_CROP_WHOLE, FD_CROP_STRIPS = 0, 1
+FD_CROP_INTS = 12
+
+
+def fd_crop_strip_width(hmax, width):
+    """output columns a workgroup of rg_bank_fd_crop_batch takes for crops of up to `hmax` rows: `width` (whole samples) or a
+    smaller multiple of 4 (strips); ValueError where width is no multiple of 4 or no strip fits the LDS tile"""
+    sw = int(lib.rg_bank_fd_crop_regime(int(hmax), int(width)))
+    if sw < 4:
+        raise ValueError("bank_fd_crop_batch: output width %d must be a multiple of 4 and 12 x %d bytes must fit the LDS tile"
+                         % (int(width), int(hmax)))
+    return sw
+
+
+def fd_crop_regime(hmax, width):
+    """the form `bank_fd_crop_batch` takes for crops of up to `hmax` rows at this output width: FD_CROP_WHOLE (a workgroup
+    resamples a whole sample: outputs up to 32 columns wide) or FD_CROP_STRIPS (a strip of at most 32 output columns, fewer where
+    the LDS tile of `hmax` rows is the limit)"""
+    return FD_CROP_WHOLE if fd_crop_strip_width(hmax, width) == int(width) else FD_CROP_STRIPS
+
+
+class FDCropDraws(object):
+    """One stage-I batch's rows and draws in ONE int32 host buffer [N, 12] = (bank row, x1, y1, w, h, flip, er0, ec0, eh, ew, rgb,
+    0), and (after `to`) its single device copy."""
+
+    __slots__ = ("host", "dev")
+
+    def __init__(self, rows):
+        rows = torch.as_tensor(rows)
+        if rows.is_cuda or rows.dtype not in (torch.int32, torch.int64):
+            raise ValueError("fd_crop_draws: the draws must be a host tensor of int32 / int64 (they are checked on the host)")
+        if rows.dim() != 2 or rows.shape[1] != 11 or rows.shape[0] == 0:
+            raise ValueError("fd_crop_draws: the draws must be [N, 11] with N > 0, got %s" % (tuple(rows.shape),))
+        if int(rows.min()) < -2 ** 31 or int(rows.max()) >= 2 ** 31:
+            raise ValueError("fd_crop_draws: the draws do not fit int32")
+        self.host = torch.zeros((rows.shape[0], FD_CROP_INTS), dtype=torch.int32)
+        self.host[:, :11].copy_(rows)
+        self.dev = None
+
+    def to(self, device):
+        """the one host->device copy of the batch"""
+        self.dev = self.host.to(device, non_blocking=True)
+        return self
+
+    def check(self, who, sizes, H, W):
+        """ValueError unless, against the HOST size table `sizes` int [M, 2] = (H_m, W_m): 0 <= row < M, 1 <= w, 1 <= h, x1 >= 0,
+        y1 >= 0, x1 + w <= W_m, y1 + h <= H_m, flip in {0, 1}, every patch (eh > 0) has ew > 0 and lies inside [0, H) x [0, W),
+        and 0 <= rgb < 2^24."""
+        p = self.host.long()
+        M = int(sizes.shape[0])
+        if int(p[:, 0].min()) < 0 or int(p[:, 0].max()) >= M:
+            raise ValueError("%s: bank row index outside [0, %d)" % (who, M))
+        hw = torch.as_tensor(sizes).long()[p[:, 0]]
+        x1, y1, w, h = p[:, 1], p[:, 2], p[:, 3], p[:, 4]
+        if bool(((w < 1) | (h < 1) | (x1 < 0) | (y1 < 0) | (x1 + w > hw[:, 1]) | (y1 + h > hw[:, 0])).any()):
+            raise ValueError("%s: crop box outside its image" % who)
+        if bool(((p[:, 5] != 0) & (p[:, 5] != 1)).any()):
+            raise ValueError("%s: flip must be 0 or 1" % who)
+        er0, ec0, eh, ew = p[:, 6], p[:, 7], p[:, 8], p[:, 9]
+        if bool((eh < 0).any()) or bool((ew < 0).any()):
+            raise ValueError("%s: negative patch size" % who)
+        if bool(((eh > 0) & ((ew <= 0) | (er0 < 0) | (ec0 < 0) | (er0 + eh > H) | (ec0 + ew > W))).any()):
+            raise ValueError("%s: patch outside the %dx%d output" % (who, H, W))
+        if bool(((p[:, 10] < 0) | (p[:, 10] >= 2 ** 24)).any()):
+            raise ValueError("%s: rgb must be R | G << 8 | B << 16 in [0, 2^24)" % who)
+
+
+def fd_crop_draws(rows, device=None):
+    """FDCropDraws of host `rows` [N, 11] = (bank row, x1, y1, w, h, flip, er0, ec0, eh, ew, rgb), uploaded when `device` is given."""
+    d = FDCropDraws(rows)
+    return d if device is None else d.to(device)
+
+
+def bank_fd_crop_batch(raw, draws, lut):
+    """[N, 3, H, W] fp32: FD-GAN stage I's RandomSizedRectCrop (crop, then PIL's bilinear resize to raw.size = (H, W), in integers)
+    -> RandomSizedEarser's colour patch (on the bytes) -> flip -> ToTensor -> Normalize of the images of the raw bank `raw`
+    (DeviceRawBank: data, offsets, sizes, sizes_host, table_x, table_y, size) named by draws.host [N, 12]; one launch
+    (rg_bank_fd_crop_batch)."""
+    H, W = int(raw.size[0]), int(raw.size[1])
+    if not isinstance(draws, FDCropDraws):
+        raise TypeError("bank_fd_crop_batch: draws must come from ops.fd_crop_draws (they are checked on the host before the launch)")
+    draws.check("bank_fd_crop_batch", raw.sizes_host, H, W)      # the draws first: a bad one is refused wherever the bank lives
+    data = _chk_rr(raw.data, "raw bank", dtype=torch.uint8, dim=1)
+    offsets = _chk_rr(raw.offsets, "offsets", dtype=torch.int64, dim=1)
+    sizes = _chk_rr(raw.sizes, "sizes", dtype=torch.int32, dim=2)
+    tx, ty = _chk_rr(raw.table_x, "table_x", dtype=torch.int32, dim=3), _chk_rr(raw.table_y, "table_y", dtype=torch.int32, dim=3)
+    M = sizes.shape[0]
+    if offsets.numel() != M or sizes.shape[1] != 2 or tx.shape[1] != W or ty.shape[1] != H or tx.shape[2] < 3 or ty.shape[2] < 3:
+        raise ValueError("bank_fd_crop_batch: offsets %s, sizes %s, tables %s / %s disagree with each other or the %dx%d output"
+                         % (tuple(offsets.shape), tuple(sizes.shape), tuple(tx.shape), tuple(ty.shape), H, W))
+    N = draws.host.shape[0]
+    if N > 65535:
+        raise ValueError("bank_fd_crop_batch: at most 65535 samples per launch")
+    hmax = int(draws.host[:, 4].max())
+    if int(draws.host[:, 3].max()) > tx.shape[0] - 1 or hmax > ty.shape[0] - 1:
+        raise ValueError("bank_fd_crop_batch: a crop is larger than the coefficient tables (%d x %d)" % (ty.shape[0] - 1, tx.shape[0] - 1))
+    fd_crop_strip_width(hmax, W)
+    if draws.dev is None:
+        draws.to(data.device)
+    if draws.dev.device != data.device:
+        raise RuntimeError("bank_fd_crop_batch: the draws were uploaded to %s, the bank lives on %s" % (draws.dev.device, data.device))
+    lut = _chk_lut("bank_fd_crop_batch", lut)
+    out = torch.empty((N, 3, H, W), dtype=torch.float32, device=data.device)
+    lib.rg_bank_fd_crop_batch(_p(data), _p(offsets), _p(sizes), M, _p(tx), tx.shape[2], tx.shape[0] - 1, _p(ty), ty.shape[2],
+                              ty.shape[0] - 1, _p(draws.dev), _p(lut), _p(out), N, H, W, hmax, _stream())
     return out

@@ -79,7 +79,7 @@ FAMILY = {
     "bicubic_norm_bwd_kernel": "misc", "bicubic_norm_fwd_kernel": "misc",
     "add_outer_terms_kernel": "misc", "row_sqsum_kernel": "misc", "segment_mean_kernel": "misc", "topk_rows_kernel": "misc",
     "erase_rects_kernel": "misc", "flip_pad_crop_kernel": "misc", "pose_maps_kernel": "misc",
-    "bank_image_kernel": "misc", "bank_pose_kernel": "misc", "bank_fd_pose_kernel": "misc",                   # databank.hip
+    "bank_image_kernel": "misc", "bank_pose_kernel": "misc", "bank_fd_pose_kernel": "misc", "bank_fd_crop_kernel": "misc",     # databank.hip
     "rerank_expand_kernel": "misc", "rerank_weights_kernel": "misc", "rerank_qe_kernel": "misc", "rg_scan_kernel": "misc",      # rg_common.h
     "rerank_col_count_kernel": "misc", "rerank_col_fill_kernel": "misc", "rerank_jaccard_kernel": "misc",
     "rerank_sq_colmax_kernel": "misc", "rerank_orig_dist_kernel": "misc",
