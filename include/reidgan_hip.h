@@ -513,6 +513,32 @@ int rg_rank_eval(const void* dist, int is_double, int Q, int G, int64_t ld, cons
                  const int* query_cams, const int* gallery_cams, int separate_camera_set, int topk, int chunk, int* npos, double* ap,
                  int* first, int* hits, int* counts, double* sums, rg_stream_t stream);
 
+/* ---- single-gallery-shot CMC (the reference's `cuhk03` protocol, `cmc(single_gallery_shot=True)` :53-75) on the same matrix
+ * (csrc/cmc_shot.hip).  The gallery is grouped by identity by the caller: seg_ptr [nid + 1] and seg_perm [G] (identities
+ * ascending, the entries of one in ascending j), query_seg [Q] = the segment of the query's identity or -1; 1 <= nid <= 4096.
+ * Rows are ordered by the stable key (d, j), by value (-0.0 == 0.0).  valid_j as above.
+ * rg_cmc_shot_order, per query i: n[i] = identities with a valid entry (0: no valid match, the query is skipped and draws
+ *   nothing), slot[i][0:n) = their segment indices by smallest valid key = the order the reference draws for them,
+ *   high[i][0:n) = their valid counts in that order; slot = -1 and high = 0 beyond n (both [Q][nid]).  status: bit 0 a NaN
+ *   in the matrix, bit 1 a seg_perm entry outside [0, G) (results then unspecified, nothing is accessed out of bounds).
+ * rg_cmc_shot_rank, queries [q0, q0 + nq) of the Q rows: draws + draw_off[i - q0] is query i's [repeat][n[i]] block of draws
+ *   u[r][p] in [0, high[i][p]) (int32, position order; never read for a skipped query).  With t_r the u[r][own]-th valid
+ *   entry of the own identity in key order and c_x(t) the valid entries of x with key < t:
+ *   rank[i][r] = #{x != own : u[r][x] < c_x(t_r)} (the true rank, also when >= topk; -1 for a skipped query) and
+ *   hist[rank] += 1 when rank < topk (hist [topk] is NOT zeroed here: launches over chunks of queries add up).
+ *   1 <= repeat <= 64.  Finding t_r is quadratic in the own identity's valid entries.
+ * rg_cmc_shot_regime: where the rank pass gathers a row's entries from (a value, not a status; -1 outside the limits):
+ *   1 the row staged in LDS with 16-byte loads (G * element size <= 32 768 bytes), 0 global memory.
+ * Integer atomics only: the same bits for any arrival order, stream or chunking. */
+int64_t rg_cmc_shot_regime(int G, int nid, int is_double);
+int rg_cmc_shot_order(const void* dist, int is_double, int Q, int G, int64_t ld, int nid, const int* seg_ptr, const int* seg_perm,
+                      const int* gallery_cams, const int* query_seg, const int* query_cams, int separate_camera_set, int* n,
+                      int* slot, int* high, int* status, rg_stream_t stream);
+int rg_cmc_shot_rank(const void* dist, int is_double, int Q, int q0, int nq, int G, int64_t ld, int nid, const int* seg_ptr,
+                     const int* seg_perm, const int* gallery_cams, const int* query_seg, const int* query_cams,
+                     int separate_camera_set, const int* n, const int* slot, const int* draws, const int64_t* draw_off, int repeat,
+                     int topk, int* rank, int* hist, rg_stream_t stream);
+
 /* ---- conv + frozen-statistics BatchNorm fold (E / D_id of FD-GAN: set_bn_fix, FD/fdgan/networks.py:57-60 with
  * trainable affine parameters, model.py:72-85).  Forward: rg_conv2d_fwd with scale/shift from rg_bn_fold — the
  * pre-normalisation tensor is never written.  Backward without it:

@@ -6,9 +6,9 @@ from __future__ import absolute_import
 from rg_hip.overlay import extend as _rg_extend  # noqa: E402
 _rg_extend(globals())                      # see rg_hip/overlay.py: reference-only sub-modules (classification) stay importable
 
-from .ranking import cmc, mean_ap  # noqa: E402
+from .ranking import cmc, mean_ap, cmc_single_shot  # noqa: E402
 
-__all__ = ['cmc', 'mean_ap']
+__all__ = ['cmc', 'mean_ap', 'cmc_single_shot']
 
 try:
     from .classification import accuracy  # noqa: E402,F401

@@ -10,9 +10,11 @@ Ties: average precision groups equal distances (as scikit-learn does), so mAP do
 CMC ranks are those of a stable sort by (distance, gallery index), where the reference's quicksort leaves them unspecified.
 A NaN in the matrix raises ValueError.
 
-`cmc(single_gallery_shot=True)` draws from numpy's global generator in a Python loop and the draws define the result: it is
-not moved to the device.  With the reference tree behind this one on sys.path the call is handed to the reference's own
-function; without one it raises NotImplementedError.
+`cmc(single_gallery_shot=True)` draws from numpy's global generator in a Python loop and the draws define the result: that
+call is not moved to the device.  With the reference tree behind this one on sys.path it is handed to the reference's own
+function; without one it raises NotImplementedError.  The opt-in is `cmc_single_shot`, a name of its own: the same protocol
+with the draws made on the host in ONE `randint` call that consumes exactly the stream of the reference's loop (same values,
+same generator state afterwards), and the ranks counted on the device (csrc/cmc_shot.hip) — no copy of the matrix, no sort.
 """
 from __future__ import absolute_import
 
@@ -23,7 +25,7 @@ import torch
 
 from rg_hip import ops, search
 
-__all__ = ['cmc', 'mean_ap']
+__all__ = ['cmc', 'mean_ap', 'cmc_single_shot']
 
 
 def _dist_on_device(distmat):
@@ -122,7 +124,8 @@ def cmc(distmat, query_ids=None, gallery_ids=None,
         ref = _reference_ranking()
         if ref is None:
             raise NotImplementedError("cmc(single_gallery_shot=True) samples the gallery with numpy's global generator on the host "
-                                      "and is not implemented on the device; it needs the reference tree behind this one")
+                                      "and is not implemented on the device; it needs the reference tree behind this one "
+                                      "(cmc_single_shot is the device-resident form of the same protocol)")
         host = distmat.detach().cpu() if torch.is_tensor(distmat) else distmat
         return ref.cmc(host, query_ids, gallery_ids, query_cams, gallery_cams, topk=topk, separate_camera_set=separate_camera_set,
                        single_gallery_shot=True, first_match_break=first_match_break)
@@ -135,3 +138,39 @@ def mean_ap(distmat, query_ids=None, gallery_ids=None,
             query_cams=None, gallery_cams=None):
     res = _score(distmat, query_ids, gallery_ids, query_cams, gallery_cams, 1, False)
     return float(res["ap_sum"] / res["num_valid"])
+
+
+def cmc_single_shot(distmat, query_ids=None, gallery_ids=None, query_cams=None, gallery_cams=None, topk=100,
+                    separate_camera_set=False, first_match_break=False, repeat=10, random_state=None, chunk=0, debug=False):
+    """The reference's `cmc(single_gallery_shot=True)` (:53-75; `repeat` is its constant 10) without the matrix leaving the
+    device: `ops.cmc_shot` finds, per query, the order in which the reference draws for the gallery identities and their valid
+    counts, the draws are ONE `randint` call on the host, and the device counts the rank of every (query, repeat).  Inputs are
+    coerced as in `cmc`.  random_state None draws from numpy's global generator, so the same `np.random.seed` gives the
+    reference's curve and leaves the generator in the reference's state; a `np.random.RandomState` is drawn from instead.
+    Returns (hist * w).cumsum() / num_valid, float64 [topk], with w = 1 under first_match_break (the reference then adds 1 per
+    repeat, `repeat` per query) and 1 / repeat otherwise.  Ties in a row are ordered by (distance, gallery index).  Every
+    argument check and the NaN check (ValueError) come before the first draw.  chunk = queries per rank launch (0 = automatic);
+    the result and the generator state do not depend on it.  debug=True returns (curve, {"n", "slot", "high", "rank" (device),
+    "hist" (host), "num_valid"})."""
+    topk, repeat = int(topk), int(repeat)
+    if repeat < 1 or repeat > ops.CMC_SHOT_MAX_REPEAT:
+        raise ValueError("cmc_single_shot: repeat must be 1 .. %d, got %d" % (ops.CMC_SHOT_MAX_REPEAT, repeat))
+    if topk < 1:
+        raise ValueError("cmc_single_shot: topk must be at least 1, got %d" % topk)
+    shape = tuple(distmat.shape) if torch.is_tensor(distmat) else np.shape(distmat)
+    if len(shape) != 2:
+        raise ValueError("distmat must be a [query, gallery] matrix, got shape %s" % (shape,))
+    m, n = shape
+    ids = _fill_defaults(m, n, query_ids, gallery_ids, query_cams, gallery_cams)
+    names = ("query_ids", "gallery_ids", "query_cams", "gallery_cams")
+    host = torch.device("cpu")
+    ids = [v if torch.is_tensor(v) and v.is_cuda else _ids_on_device(v, nm, k, host) for v, nm, k in zip(ids, names, (m, n, m, n))]
+    d = _dist_on_device(distmat)
+    qi, gi, qc, gc = (_ids_on_device(v, nm, k, d.device) for v, nm, k in zip(ids, names, (m, n, m, n)))
+    res = ops.cmc_shot(d, qi, gi, qc, gc, topk=topk, separate_camera_set=bool(separate_camera_set), repeat=repeat,
+                       random_state=random_state, chunk=chunk, debug=debug)
+    if res["num_valid"] == 0:
+        raise RuntimeError("No valid query")
+    w = 1.0 if first_match_break else 1.0 / repeat
+    curve = (res["hist"] * w).cumsum() / res["num_valid"]
+    return (curve, res) if debug else curve

@@ -12,7 +12,8 @@ top-k gallery rows of ALL queries are gathered into one [Q * k, 2048] operand an
 (x1 - x2)^2 -> BatchNorm1d -> Linear) runs once.  The merge of the two stages (:215-225) is unchanged arithmetic.
 
 Device-resident counterparts under names of their own, which need no reference tree: `extract_features_device`,
-`evaluate_all_device` and `DeviceCascadeEvaluator`.  Its second stage gathers the pairs inside `ops.pair_score`
+`evaluate_all_device` (and `evaluate_all_single_shot`, which also scores the `cuhk03` column on the device) and
+`DeviceCascadeEvaluator`.  Its second stage gathers the pairs inside `ops.pair_score`
 (csrc/cascade.hip: no [Q * k, 2048] operand is ever built) and merges in place on the device with `ops.cascade_merge`.
 The collection loop behind `extract_features_device` is rg_hip/hostloop.py's and the opening of `evaluate_all_device` is
 `clustercontrast.evaluators.score_mean_ap`.
@@ -128,9 +129,25 @@ def evaluate_all_device(distmat, query=None, gallery=None,
     """The reference's `evaluate_all` (:101-181): same signature, printed lines and return values, from ONE `ops.rank_eval` pass
     over the (device) matrix, which yields mAP, the `allshots` and the `market1501` CMC together.  top1=False returns the mAP; a
     named dataset other than 'cuhk03' returns (market1501 top-1, mAP).
-    The `cuhk03` column (single_gallery_shot=True) goes through this build's `cmc`, which hands it to the reference's host
-    sampling: with dataset=None and with dataset='cuhk03' a run without the reference tree ends in that function's
-    NotImplementedError (after the 'Mean AP' line)."""
+    The `cuhk03` column (single_gallery_shot=True) by default goes through this build's `cmc`, which hands it to the reference's
+    host sampling: with dataset=None and with dataset='cuhk03' a run without the reference tree ends in that function's
+    NotImplementedError (after the 'Mean AP' line).  The signature stays the reference's; `evaluate_all_single_shot` is the same
+    function with the column scored on the device."""
+    return _evaluate_all(distmat, query, gallery, query_ids, gallery_ids, query_cams, gallery_cams, cmc_topk, dataset, top1, False)
+
+
+def evaluate_all_single_shot(distmat, query=None, gallery=None,
+                             query_ids=None, gallery_ids=None,
+                             query_cams=None, gallery_cams=None,
+                             cmc_topk=(1, 5, 10), dataset=None, top1=True, single_shot=True):
+    """`evaluate_all_device` with one more, last keyword, under a name of its own: the `cuhk03` column comes from
+    `cmc_single_shot` (the reference's protocol with the ranks counted on the device, separate_camera_set=True as the reference
+    configures `cuhk03`), so dataset=None and dataset='cuhk03' need no reference tree.  single_shot=True draws from numpy's
+    global generator as the reference does, a `np.random.RandomState` is drawn from instead, False is `evaluate_all_device`."""
+    return _evaluate_all(distmat, query, gallery, query_ids, gallery_ids, query_cams, gallery_cams, cmc_topk, dataset, top1, single_shot)
+
+
+def _evaluate_all(distmat, query, gallery, query_ids, gallery_ids, query_cams, gallery_cams, cmc_topk, dataset, top1, single_shot):
     from clustercontrast.evaluation_metrics import ranking as R
     from clustercontrast.evaluators import score_mean_ap
     res, mAP, (query_ids, gallery_ids, query_cams, gallery_cams) = score_mean_ap(distmat, query, gallery, query_ids, gallery_ids,
@@ -139,6 +156,9 @@ def evaluate_all_device(distmat, query=None, gallery=None,
         return mAP
 
     def cuhk03():
+        if single_shot is not False and single_shot is not None:
+            return R.cmc_single_shot(distmat, query_ids, gallery_ids, query_cams, gallery_cams, separate_camera_set=True,
+                                     first_match_break=False, random_state=None if single_shot is True else single_shot)
         return R.cmc(distmat, query_ids, gallery_ids, query_cams, gallery_cams, separate_camera_set=True,
                      single_gallery_shot=True, first_match_break=False)
     allshots = res["allshots"].cumsum() / res["num_valid"]
@@ -165,13 +185,15 @@ def evaluate_all_device(distmat, query=None, gallery=None,
 class DeviceCascadeEvaluator(object):
     """`CascadeEvaluator` with features, distances, ranking, pair scores and the merged matrix kept on the device; works with no
     reference tree.  The second stage is a device top-k, `ops.pair_score` (the embedding network on pairs gathered inside the
-    kernel: no [Q * k, D] operand) and `ops.cascade_merge` (in place)."""
+    kernel: no [Q * k, D] operand) and `ops.cascade_merge` (in place).  single_shot is `evaluate_all_single_shot`'s: False keeps the
+    `cuhk03` column with the reference's host sampling, True or a `np.random.RandomState` scores it on the device."""
 
-    def __init__(self, base_model, embed_model, embed_dist_fn=softmax_class0):
+    def __init__(self, base_model, embed_model, embed_dist_fn=softmax_class0, single_shot=False):
         super(DeviceCascadeEvaluator, self).__init__()
         self.base_model = base_model
         self.embed_model = embed_model
         self.embed_dist_fn = embed_dist_fn
+        self.single_shot = single_shot
         self.last_path = None           # 'score' / 'logits' (the fused kernel) or 'composed', and the chunks the latter took
         self.last_chunks = 0
         self.last_distmat = None        # the matrix the last `evaluate` scored (device), for callers that go on with it
@@ -229,11 +251,11 @@ class DeviceCascadeEvaluator(object):
         distmat = search.dist_block(probe, gal, 1.0, True)
         print("First stage evaluation:")
         if second_stage:
-            evaluate_all_device(distmat, query=query, gallery=gallery, dataset=dataset, top1=top1)
+            evaluate_all_single_shot(distmat, query=query, gallery=gallery, dataset=dataset, top1=top1, single_shot=self.single_shot)
             distmat = self.second_stage_device(distmat, probe, gal, rerank_topk)
             print("Second stage evaluation:")
         self.last_distmat = distmat
-        return evaluate_all_device(distmat, query, gallery, dataset=dataset, top1=top1)
+        return evaluate_all_single_shot(distmat, query, gallery, dataset=dataset, top1=top1, single_shot=self.single_shot)
 
 
 # `extract_features`, `evaluate_all`, `Evaluator` are the reference's own host code (rg_hip/overlay.py); they score through this

@@ -15,8 +15,9 @@ unit(s) it calls.
     gan        csrc/gan_extra.hip: avgpool2d, reflection padding, spectral normalisation
     pool       csrc/pool.hip, part_head.hip: maxpool, global average, GeM, part pooling, the multi-part head
     loss       csrc/loss.hip, verif_head.hip: the losses, the fused verification head
-    retrieval  csrc/cm.hip, retrieval.hip, rerank.hip, rank_eval.hip, cascade.hip: cluster memory, kNN helpers, sort segments and
-               label compaction (torch), re-ranking, CMC / mAP, the cascade's pair scores and merge
+    retrieval  csrc/cm.hip, retrieval.hip, rerank.hip, rank_eval.hip, cmc_shot.hip, cascade.hip: cluster memory, kNN helpers, sort
+               segments and label compaction (torch), re-ranking, CMC / mAP, the single-gallery-shot CMC, the cascade's pair
+               scores and merge
     dbscan     csrc/dbscan.hip
     infomap    csrc/infomap.hip: the wrappers and the host-driven search
     kmeans     csrc/kmeans.hip: assign / tally / update / split and the host loop over them
@@ -60,7 +61,9 @@ from .loss import (sigmoid_bce_fwd, sigmoid_bce_bwd, mse_const_fwd, mse_const_bw
                    verif_head_fwd, verif_head_bwd)
 from .retrieval import (cm_update, normalize_listed_rows, topk_rows, row_sqsum, add_outer_terms, segment_mean, sorted_segments,
                         compact_labels, rerank_expand, rerank_weights, rerank_query_expand, rerank_columns, rerank_jaccard,
-                        rerank_orig_dist, rerank_from_rank, rank_eval, PAIR_SCORE_MAX_C, PAIR_SCORE_MAX_D, PAIR_SCORE_MAX_Q,
+                        rerank_orig_dist, rerank_from_rank, rank_eval, CMC_SHOT_MAX_IDS, CMC_SHOT_MAX_REPEAT,
+                        CMC_SHOT_DRAW_BYTES, CMC_SHOT_GLOBAL, CMC_SHOT_LDS_ROW, cmc_shot_regime, cmc_shot_order, cmc_shot_rank,
+                        cmc_shot, PAIR_SCORE_MAX_C, PAIR_SCORE_MAX_D, PAIR_SCORE_MAX_Q,
                         CASCADE_MERGE_MAX_G, PAIR_VEC4, PAIR_SPLIT_K, pair_score_regime, pair_score, cascade_merge)
 from .dbscan import dbscan_count, dbscan_fill, dbscan_neighbors, dbscan_components, dbscan_labels, dbscan_asymmetry, dbscan
 from .infomap import (INFOMAP_MAX_N, INFOMAP_MAX_K, INFOMAP_FLOW_MAX_ITERS, INFOMAP_FLOW_BATCH, INFOMAP_SWEEP_CAP,

@@ -1,7 +1,8 @@
 """Cluster memory, kNN and row helpers of the pseudo-labelling code, k-reciprocal re-ranking, CMC / mAP scoring, the second stage
-of the cascade evaluation: csrc/cm.hip, csrc/retrieval.hip, csrc/rerank.hip, csrc/rank_eval.hip, csrc/cascade.hip."""
+of the cascade evaluation: csrc/cm.hip, csrc/retrieval.hip, csrc/rerank.hip, csrc/rank_eval.hip, csrc/cmc_shot.hip, csrc/cascade.hip."""
 from __future__ import absolute_import
 
+import numpy as np
 import torch
 
 from ._base import _chk, _chk_rr, _list_total, _p, _stream, lib
@@ -261,6 +262,156 @@ def rank_eval(dist, query_ids, gallery_ids, query_cams, gallery_cams, topk=100, 
                first_hist=counts_h[2:].astype("int64"), allshots=sums_h[1:].copy())
     if debug:
         res.update(npos=npos, ap=ap, first=first, hits=hits)
+    return res
+
+
+# ------------------------------------------------------------------------------------------------
+# single-gallery-shot CMC, the reference's `cuhk03` protocol (csrc/cmc_shot.hip): order pass, host draws, rank pass
+# ------------------------------------------------------------------------------------------------
+CMC_SHOT_MAX_IDS, CMC_SHOT_MAX_REPEAT, CMC_SHOT_DRAW_BYTES = 4096, 64, 32 << 20
+CMC_SHOT_GLOBAL, CMC_SHOT_LDS_ROW = 0, 1      # values of cmc_shot_regime
+
+
+def cmc_shot_regime(G, nid, is_double):
+    """where the rank pass gathers a row's entries from at this shape: CMC_SHOT_LDS_ROW (the row staged in LDS with 16-byte loads)
+    or CMC_SHOT_GLOBAL; -1 outside the limits"""
+    return int(lib.rg_cmc_shot_regime(int(G), int(nid), int(bool(is_double))))
+
+
+def _cmc_shot_dist(dist, who):
+    if not torch.is_tensor(dist) or dist.dtype not in (torch.float32, torch.float64):
+        raise TypeError("rg_hip: %s: dist must be an fp32 or fp64 tensor, got %s"
+                        % (who, dist.dtype if torch.is_tensor(dist) else type(dist).__name__))
+    dist = _chk_rr(dist, "dist", dist.dtype, 2)
+    if dist.shape[0] < 1 or dist.shape[1] < 1:
+        raise ValueError("rg_hip: %s: dist must be a non-empty [Q, G] matrix, got shape %s" % (who, tuple(dist.shape)))
+    return dist
+
+
+def cmc_shot_order(dist, query_ids, gallery_ids, query_cams, gallery_cams, separate_camera_set=False):
+    """Order pass of the single-gallery-shot CMC on dist [Q, G] (fp32 or fp64, on the device; ids / cams int32 device vectors as
+    for rank_eval).  Groups the gallery by identity on the host (O(G); the two id vectors are read back for it), then per query:
+    n = identities with a valid entry (0: no valid match, the query is skipped), slot[q, :n] = their indices in the order the
+    reference draws for them (first appearance in the row's stable (d, j) order), high[q, :n] = their valid counts.
+    Returns the plan the rank pass takes: {"dist", "Q", "G", "nid", "separate", "seg_ptr", "seg_perm", "gallery_cams", "query_seg",
+    "query_cams", "n", "slot", "high" (device), "n_host" [Q], "high_host" [Q, nid] (numpy int32)}.  More than 4096 identities
+    raise ValueError before anything is enqueued; a NaN in the matrix raises ValueError."""
+    dist = _cmc_shot_dist(dist, "cmc_shot_order")
+    Q, G = dist.shape
+    vecs = []
+    for t, name, n in ((query_ids, "query_ids", Q), (gallery_ids, "gallery_ids", G), (query_cams, "query_cams", Q),
+                       (gallery_cams, "gallery_cams", G)):
+        t = _chk_rr(t, name, torch.int32, 1)
+        if t.numel() != n:
+            raise ValueError("rg_hip: cmc_shot_order: %s has %d entries, dist %s needs %d" % (name, t.numel(), tuple(dist.shape), n))
+        vecs.append(t)
+    qid, gid = vecs[0].cpu().numpy(), vecs[1].cpu().numpy()
+    uniq, counts = np.unique(gid, return_counts=True)
+    nid = int(uniq.size)
+    if nid > CMC_SHOT_MAX_IDS:
+        raise ValueError("rg_hip: cmc_shot_order: at most %d gallery identities (their keys are sorted in LDS), got %d"
+                         % (CMC_SHOT_MAX_IDS, nid))
+    if Q * nid >= 2 ** 31:
+        raise ValueError("rg_hip: cmc_shot_order needs Q * nid < 2^31, got Q=%d nid=%d" % (Q, nid))
+    seg_ptr = np.zeros(nid + 1, dtype=np.int32)
+    seg_ptr[1:] = np.cumsum(counts)
+    seg_perm = np.argsort(gid, kind="stable").astype(np.int32)          # ids ascending, the entries of one in ascending j
+    pos = np.minimum(np.searchsorted(uniq, qid), nid - 1)
+    qseg = np.where(uniq[pos] == qid, pos, -1).astype(np.int32)
+    dev = dist.device
+    seg_ptr_d, seg_perm_d, qseg_d = (torch.from_numpy(a).to(dev) for a in (seg_ptr, seg_perm, qseg))
+    n = torch.empty((Q,), dtype=torch.int32, device=dev)
+    slot = torch.empty((Q, nid), dtype=torch.int32, device=dev)
+    high = torch.empty((Q, nid), dtype=torch.int32, device=dev)
+    status = torch.empty((1,), dtype=torch.int32, device=dev)
+    sep = int(bool(separate_camera_set))
+    lib.rg_cmc_shot_order(_p(dist), int(dist.dtype == torch.float64), Q, G, G, nid, _p(seg_ptr_d), _p(seg_perm_d), _p(vecs[3]),
+                          _p(qseg_d), _p(vecs[2]), sep, _p(n), _p(slot), _p(high), _p(status), _stream())
+    st = int(status.cpu().numpy()[0])
+    if st & 1:
+        raise ValueError("rg_hip: cmc_shot_order: the distance matrix holds a NaN")
+    if st:
+        raise RuntimeError("rg_hip: cmc_shot_order: broken segment list (status %d)" % st)
+    return dict(dist=dist, Q=Q, G=G, nid=nid, separate=sep, seg_ptr=seg_ptr_d, seg_perm=seg_perm_d, gallery_cams=vecs[3],
+                query_seg=qseg_d, query_cams=vecs[2], n=n, slot=slot, high=high, n_host=n.cpu().numpy(),
+                high_host=high.cpu().numpy())
+
+
+def cmc_shot_rank(plan, draws, q0, q1, repeat, topk, rank, hist):
+    """Rank pass for the queries [q0, q1) of a cmc_shot_order plan.  draws: host int32 vector, for the valid queries of the range
+    in query order the [repeat, n[q]] block of draws u[r, p] in [0, high[q, p]).  Writes rank[q0:q1] (int32 [Q, repeat] on the
+    device: the rank of the own identity among the sampled entries, -1 for a skipped query) and adds the ranks below topk into
+    hist (int32 [topk] on the device, zeroed by the caller)."""
+    Q, nid, repeat, topk, q0, q1 = plan["Q"], plan["nid"], int(repeat), int(topk), int(q0), int(q1)
+    dist = plan["dist"]
+    if not 0 <= q0 < q1 <= Q:
+        raise ValueError("rg_hip: cmc_shot_rank: queries [%d, %d) outside the %d rows" % (q0, q1, Q))
+    if not 1 <= repeat <= CMC_SHOT_MAX_REPEAT or topk < 1 or Q * repeat >= 2 ** 31:
+        raise ValueError("rg_hip: cmc_shot_rank needs 1 <= repeat <= %d, topk >= 1 and Q * repeat < 2^31, got repeat=%d topk=%d Q=%d"
+                         % (CMC_SHOT_MAX_REPEAT, repeat, topk, Q))
+    rank, hist = _chk_rr(rank, "rank", torch.int32, 2), _chk_rr(hist, "hist", torch.int32, 1)
+    if tuple(rank.shape) != (Q, repeat) or hist.numel() != topk:
+        raise ValueError("rg_hip: cmc_shot_rank: rank %s must be [%d, %d] and hist %s [%d]"
+                         % (tuple(rank.shape), Q, repeat, tuple(hist.shape), topk))
+    draws = np.ascontiguousarray(draws)
+    off = np.zeros(q1 - q0 + 1, dtype=np.int64)
+    np.cumsum(plan["n_host"][q0:q1].astype(np.int64) * repeat, out=off[1:])
+    if draws.dtype != np.int32 or draws.ndim != 1 or draws.size != off[-1]:
+        raise ValueError("rg_hip: cmc_shot_rank: draws must be an int32 vector of %d entries, got %s %s"
+                         % (off[-1], draws.dtype, draws.shape))
+    dev = dist.device
+    draws_d = torch.from_numpy(draws if draws.size else np.zeros(1, dtype=np.int32)).to(dev)
+    off_d = torch.from_numpy(off[:-1].copy()).to(dev)
+    lib.rg_cmc_shot_rank(_p(dist), int(dist.dtype == torch.float64), Q, q0, q1 - q0, plan["G"], plan["G"], nid, _p(plan["seg_ptr"]),
+                         _p(plan["seg_perm"]), _p(plan["gallery_cams"]), _p(plan["query_seg"]), _p(plan["query_cams"]),
+                         plan["separate"], _p(plan["n"]), _p(plan["slot"]), _p(draws_d), _p(off_d), repeat, topk, _p(rank), _p(hist),
+                         _stream())
+    return rank
+
+
+def cmc_shot(dist, query_ids, gallery_ids, query_cams, gallery_cams, topk=100, separate_camera_set=False, repeat=10,
+             random_state=None, chunk=0, debug=False):
+    """The whole single-gallery-shot scoring: order pass, host draws, rank pass.  {"hist" int64 [topk] (host): the (query, repeat)
+    pairs whose sampled rank is the bin, "num_valid": the queries with a valid match}; debug=True adds the device tensors "n",
+    "slot", "high", "rank".  The draws are ONE stream of `random_state.randint(0, highs)` over, for the valid queries in query
+    order, np.tile(high[q, :n[q]], repeat) — what the reference's np.random.choice loop consumes, so the generator is left where
+    the reference leaves it; random_state None is numpy's global generator.  chunk = queries per rank launch (0: as many as keep
+    one launch's draws at or below 32 MB); the stream, the bits and the generator state do not depend on it.  Every check,
+    the NaN check included, comes before the first draw."""
+    topk, repeat, chunk = int(topk), int(repeat), int(chunk)
+    if not 1 <= repeat <= CMC_SHOT_MAX_REPEAT:
+        raise ValueError("rg_hip: cmc_shot: repeat must be 1 .. %d, got %d" % (CMC_SHOT_MAX_REPEAT, repeat))
+    if topk < 1:
+        raise ValueError("rg_hip: cmc_shot: topk must be at least 1, got %d" % topk)
+    if chunk < 0:
+        raise ValueError("rg_hip: cmc_shot: chunk must be 0 (automatic) or a number of queries, got %d" % chunk)
+    rs = np.random if random_state is None else random_state
+    if not callable(getattr(rs, "randint", None)):
+        raise TypeError("rg_hip: cmc_shot: random_state must be None or a numpy.random.RandomState, got %s" % type(random_state).__name__)
+    plan = cmc_shot_order(dist, query_ids, gallery_ids, query_cams, gallery_cams, separate_camera_set)
+    Q, dev = plan["Q"], plan["dist"].device
+    if Q * repeat >= 2 ** 31:
+        raise ValueError("rg_hip: cmc_shot needs Q * repeat < 2^31, got Q=%d repeat=%d" % (Q, repeat))
+    n_h, high_h = plan["n_host"], plan["high_host"]
+    rank = torch.empty((Q, repeat), dtype=torch.int32, device=dev)
+    hist = torch.zeros((topk,), dtype=torch.int32, device=dev)
+    per_query = n_h.astype(np.int64) * repeat * 4
+    q0 = 0
+    while q0 < Q:
+        if chunk:
+            q1 = min(Q, q0 + chunk)
+        else:
+            q1 = q0 + max(1, int(np.searchsorted(np.cumsum(per_query[q0:]), CMC_SHOT_DRAW_BYTES, side="right")))
+        highs = [np.tile(high_h[q, :n_h[q]], repeat) for q in range(q0, q1) if n_h[q] > 0]
+        if highs:
+            draws = rs.randint(0, np.concatenate(highs)).astype(np.int32)
+        else:
+            draws = np.zeros(0, dtype=np.int32)
+        cmc_shot_rank(plan, draws, q0, q1, repeat, topk, rank, hist)
+        q0 = q1
+    res = dict(hist=hist.cpu().numpy().astype(np.int64), num_valid=int((n_h > 0).sum()))
+    if debug:
+        res.update(n=plan["n"], slot=plan["slot"], high=plan["high"], rank=rank)
     return res
 
 

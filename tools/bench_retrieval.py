@@ -33,7 +33,14 @@ from the state three iterations into a run: device events around `assign`, `tall
 in the same pass and process, the composition the library offered before them — `ops.linear_fwd` (the [N, K] product),
 `ops.add_outer_terms`, `ops.topk_rows(k=1)`, then a stable `torch.sort` of the labels with the segment offsets and
 `ops.segment_mean` — which writes and re-reads the [N, K] score matrix; one warm-up pass, medians with min / max of the two
-per-pass sums; and the wall time of the whole `ops.kmeans` run with its iterations."""
+per-pass sums; and the wall time of the whole `ops.kmeans` run with its iterations.
+
+`--single-shot [Q,G] [--noise X] [--out FILE]` (default 3368,15913 with the synthetic identities of `--evaluate`, the `cuhk03`
+configuration separate_camera_set=True, repeat 10) times the single-gallery-shot CMC: device events around `rg_cmc_shot_order`
+and around the `rg_cmc_shot_rank` launches of all chunks (draws already on the device), on the fp32 matrix and on its fp64 copy
+(the two gather regimes at this size); the wall time of the copy of `n` and `high` to the host, of the host draws (`randint`
+plus the int32 conversion) and of the draw upload; and `cmc_single_shot` end to end; one warm-up pass, medians of `--reps`.
+There is no host path to put beside it without a reference tree, so no ratio is printed.  --out appends the JSON line to FILE."""
 import os, sys, time, json
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "reid-gan_amd"))
@@ -345,6 +352,113 @@ def evaluate_mode(spec, reps, noise):
                         "mean_ap_abs_diff": float(abs(want[0] - mean_ap(dist, qid, gid, qcam, gcam)))}
     print(json.dumps(res))
 
+
+def single_shot_mode(spec, reps, noise, out_path=None):
+    import numpy as np
+    from rg_hip.lib import lib
+    from clustercontrast.evaluation_metrics import cmc_single_shot
+    Q, G = (int(v) for v in spec.split(","))
+    D, n_id, n_cam, topk, repeat = 128, 751, 6, 100, 10
+    g = torch.Generator(device=dev).manual_seed(0)
+    centres = F.normalize(torch.randn(n_id, D, generator=g, device=dev), dim=1)
+    ids = torch.randint(0, n_id, (Q + G,), generator=g, device=dev)
+    cams = torch.randint(0, n_cam, (Q + G,), generator=g, device=dev).int()
+    x = F.normalize(centres[ids] + noise * torch.randn(Q + G, D, generator=g, device=dev) / D ** 0.5, dim=1)
+    ids = ids.int()
+    qid, gid, qcam, gcam = ids[:Q].contiguous(), ids[Q:].contiguous(), cams[:Q].contiguous(), cams[Q:].contiguous()
+    dist = dist_block(x[:Q].contiguous(), x[Q:].contiguous(), 1.0, True)
+    mats = {"fp32": dist, "fp64": dist.double()}
+    p = ops._p
+    med, spread, regimes = {}, {}, {}
+    plan = None
+    for tag, d in mats.items():
+        plan = ops.cmc_shot_order(d, qid, gid, qcam, gcam, True)
+        regimes[tag] = ops.cmc_shot_regime(G, plan["nid"], tag == "fp64")
+        n_h, high_h = plan["n_host"], plan["high_host"]
+        # the chunks `ops.cmc_shot` takes, their draws made and uploaded ahead of the timed launches
+        per_query, bounds, q0 = n_h.astype(np.int64) * repeat * 4, [], 0
+        while q0 < Q:
+            q1 = q0 + max(1, int(np.searchsorted(np.cumsum(per_query[q0:]), ops.CMC_SHOT_DRAW_BYTES, side="right")))
+            bounds.append((q0, q1))
+            q0 = q1
+        rs = np.random.RandomState(0)
+        chunks = []
+        for q0, q1 in bounds:
+            highs = np.concatenate([np.tile(high_h[q, :n_h[q]], repeat) for q in range(q0, q1) if n_h[q] > 0])
+            off = np.zeros(q1 - q0, dtype=np.int64)
+            off[1:] = np.cumsum(n_h[q0:q1 - 1].astype(np.int64) * repeat)
+            chunks.append((q0, q1, torch.from_numpy(rs.randint(0, highs).astype(np.int32)).to(dev), torch.from_numpy(off).to(dev)))
+        rank = torch.empty((Q, repeat), dtype=torch.int32, device=dev)
+        hist = torch.zeros(topk, dtype=torch.int32, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        samples = {"order": [], "rank": []}
+        for it in range(reps + 1):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            ev[0].record()
+            lib.rg_cmc_shot_order(p(d), int(tag == "fp64"), Q, G, G, plan["nid"], p(plan["seg_ptr"]), p(plan["seg_perm"]), p(gcam),
+                                  p(plan["query_seg"]), p(qcam), 1, p(plan["n"]), p(plan["slot"]), p(plan["high"]), p(status), ops._stream())
+            ev[1].record()
+            for q0, q1, draws_d, off_d in chunks:
+                lib.rg_cmc_shot_rank(p(d), int(tag == "fp64"), Q, q0, q1 - q0, G, G, plan["nid"], p(plan["seg_ptr"]), p(plan["seg_perm"]),
+                                     p(gcam), p(plan["query_seg"]), p(qcam), 1, p(plan["n"]), p(plan["slot"]), p(draws_d), p(off_d),
+                                     repeat, topk, p(rank), p(hist), ops._stream())
+            ev[2].record()
+            torch.cuda.synchronize()
+            if it:                                   # pass 0 is the warm-up
+                samples["order"].append(ev[0].elapsed_time(ev[1]))
+                samples["rank"].append(ev[1].elapsed_time(ev[2]))
+        for k, v in samples.items():
+            med["%s_%s" % (k, tag)] = round(float(np.median(v)), 3)
+            spread["%s_%s" % (k, tag)] = [round(min(v), 3), round(max(v), 3)]
+        del chunks
+    # host steps on the fp32 plan: the copy of n and high, the draws of all chunks, their upload
+    n_h, high_h = plan["n_host"], plan["high_host"]
+    host = {"highs_copy": [], "draws": [], "upload": []}
+    highs_all = np.concatenate([np.tile(high_h[q, :n_h[q]], repeat) for q in range(Q) if n_h[q] > 0])
+    for it in range(reps + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        plan["n"].cpu().numpy(); plan["high"].cpu().numpy()
+        t1 = time.perf_counter()
+        draws = np.random.RandomState(it).randint(0, highs_all).astype(np.int32)
+        t2 = time.perf_counter()
+        torch.from_numpy(draws).to(dev)
+        torch.cuda.synchronize()
+        t3 = time.perf_counter()
+        if it:
+            for k, v in zip(("highs_copy", "draws", "upload"), (t1 - t0, t2 - t1, t3 - t2)):
+                host[k].append(v * 1e3)
+    wall = {}
+    for tag, d in mats.items():
+        w = []
+        for it in range(reps + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            curve = cmc_single_shot(d, qid, gid, qcam, gcam, topk=topk, separate_camera_set=True, random_state=np.random.RandomState(0))
+            if it:
+                w.append((time.perf_counter() - t0) * 1e3)
+        wall[tag] = round(float(np.median(w)), 1)
+    res = {"single_shot": {"Q": Q, "G": G, "D": D, "identities": int(plan["nid"]), "cameras": n_cam, "topk": topk, "repeat": repeat,
+                           "separate_camera_set": True, "noise": noise, "reps": reps},
+           "regime": regimes, "kernel_ms_median": med, "kernel_ms_min_max": spread, "matrix_MB_fp32": round(Q * G * 4 / 1e6, 1),
+           "draws": int(highs_all.size), "draw_MB": round(highs_all.size * 4 / 1e6, 1), "valid_queries": int((n_h > 0).sum()),
+           "host_ms_median": {k: round(float(np.median(v)), 2) for k, v in host.items()},
+           "cmc_single_shot_wall_ms_median": wall, "top1": round(float(curve[0]), 6)}
+    line = json.dumps(res)
+    print(line)
+    if out_path:
+        with open(out_path, "a") as f:
+            f.write(line + "\n")
+
+
+if "--single-shot" in sys.argv:
+    _i = sys.argv.index("--single-shot") + 1
+    _spec = sys.argv[_i] if _i < len(sys.argv) and not sys.argv[_i].startswith("--") else "3368,15913"
+    _reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 5
+    _noise = float(sys.argv[sys.argv.index("--noise") + 1]) if "--noise" in sys.argv else 0.90
+    _out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
+    single_shot_mode(_spec, _reps, _noise, _out)
+    sys.exit(0)
 
 if "--evaluate" in sys.argv:
     _i = sys.argv.index("--evaluate") + 1

@@ -98,6 +98,8 @@ FAMILY = {
     "kmeans_order_kernel": "misc", "kmeans_update_kernel": "misc", "kmeans_csq_kernel": "misc", "kmeans_split_kernel": "misc",
     # rank_eval.hip
     "rank_eval_row_kernel": "misc", "rank_eval_reduce_kernel": "misc",
+    # cmc_shot.hip
+    "cmc_shot_order_kernel": "misc", "cmc_shot_rank_kernel": "misc",
     # cascade.hip
     "pair_score_kernel": "misc", "cascade_merge_kernel": "misc",
 }
